@@ -27,6 +27,16 @@ Workload (3-D 7-point Laplacian of the reference's tst/laplacian generator, kapp
 inside the timed steps / their HIP-event time on the launch stream, summed over ranks.  Setup and solve seconds are
 reported next to it (`setup_s`, `solve_s`; `ms_per_step` = wall clock of the K steps / K).  `roofline` describes the
 kernel that owns the largest share of the step; `roofline.kernels` lists every hot kernel class with its share.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures or checks
+runs only with --full: the untimed step with HIP graphs and its true residual, the PMC traffic / MFMA figures attached
+from profiles/, the comparison with the oracle's golden of the grid, the heat workload's plain-ASM count, the
+HBM-resident SpMV, the CPU baseline with its parity sample, and the one-GPU anchor of the weak N > 1 lines.
+
+--dump-outputs DIR writes what the timed path computed in its LAST timed step as DIR/<name>.npy (float64): the solution
+(every owned row up to 2 M, above that a fixed seeded sample of 2 M rows, with their global indices in x_index.npy), the
+residual history, the kept eigenvector count of every subdomain of the rank, and iterations / final residual norm /
+dimE.  N > 1: rank 0's rows.  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -50,6 +60,22 @@ KERNEL_CLASSES = [(0, "k_spmv_sell (fine-level CSR SpMV)", "hbm"), (1, "k_spmm_s
                   (2, "k_gram_flat (Rayleigh-Ritz Gram, FP64 MFMA; k_gram_mfma for other shapes)", "mfma"),
                   (3, "k_lobpcg_update32 (LOBPCG block update [X' P'] = S C, FP64 MFMA; lean iteration: S alone, the residual comes from the two-operator SpMM)", "mfma"),
                   (4, "k_spmv_sell_lp (V-cycle of the local solves: fine-level passes over the float / 16-bit-column companions)", "hbm")]
+
+
+DUMP_X_ROWS = 2_000_000     # solution rows written by --dump-outputs: 16 MB of values + 16 MB of their global indices
+
+
+def dump_outputs(out_dir, x, owned, its, rnorm, dim_e, history, local_dims):
+    """--dump-outputs: the results of the last timed step as float64 .npy files (see the module docstring)"""
+    os.makedirs(out_dir, exist_ok=True)
+    owned = np.asarray(owned, dtype=np.int64)
+    if len(x) > DUMP_X_ROWS:        # a fixed seeded sample of the rows: the same rows for the same arguments
+        sel = np.sort(np.random.default_rng(20240601).choice(len(x), size=DUMP_X_ROWS, replace=False))
+        x, owned = x[sel], owned[sel]
+    arrays = {"x": x, "x_index": owned, "residual_history": history, "local_dims": local_dims,
+              "iterations": [its], "rnorm": [rnorm], "dimE": [dim_e]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def rank_grid(n_ranks):
@@ -109,6 +135,12 @@ def build_parser():
     ap.add_argument("--comm", default=os.environ.get("GENEO_BENCH_COMM", "rccl"), choices=("rccl", "torch", "staged"),
                     help="N > 1 transport: rccl = C++ ncclSend/Recv + ncclAllReduce inside libgeneopc (default); "
                          "torch = torch.distributed callbacks; staged = host-staged gloo (ranks may share a GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the untimed HIP-graph step and its "
+                         "true residual, PMC / MFMA figures from profiles/, the oracle golden of the grid, the heat workload's "
+                         "ASM,0 count, the HBM-resident SpMV, the CPU baseline and parity sample, the weak N > 1 one-GPU anchor")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     return ap
 
 
@@ -154,19 +186,26 @@ def build_problem(args, rank, size):
     nb = len(sub_rank)
     my = [s for s in range(nb) if sub_rank[s] == rank]
     # the rank's subdomains side by side (the generator and the decomposition are C++ calls and numpy passes that release
-    # the interpreter lock: 368^3 on one rank, eight 6.5 M-row subdomains: 33 s one after the other)
+    # the interpreter lock: 368^3 on one rank, eight 6.5 M-row subdomains: 33 s one after the other; on 8 cores 20 s with
+    # 4 threads, 12 s with 8).  Each subdomain is built on its own: the result does not depend on the thread count.
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(4, max(1, len(my)))) as ex:
+    with ThreadPoolExecutor(max_workers=min(8, max(1, len(my)))) as ex:
         doms = list(ex.map(lambda s: decomp.decompose_grid_domain(n, 3, parts, args.overlap, s, native=True), my))
     plan = decomp.grid_rank_plan(n, 3, parts, args.overlap, sub_rank, rank, size, doms)
-    # b = A (1, 2, ..., N) (driver:820-831) on the owned rows
+    # b = A (1, 2, ..., N) (driver:820-831) on the owned rows: every row from the subdomain that owns its node, so the
+    # subdomains' parts are disjoint and are computed side by side
     npart_of = lambda gid: ((gid % n) * parts[0]) // n + parts[0] * ((((gid // n) % n) * parts[1]) // n
                                                                      + parts[1] * (((gid // (n * n)) * parts[2]) // n))
-    b = np.zeros(len(plan.owned))
-    for d in doms:
+
+    def rhs_part(d):
         rows = d.a_dir @ (d.l2g.astype(np.float64) + 1.0)
         sel = npart_of(d.l2g) == d.gid
-        b[np.searchsorted(plan.owned, d.l2g[sel])] = rows[sel]
+        return np.searchsorted(plan.owned, d.l2g[sel]), rows[sel]
+
+    b = np.zeros(len(plan.owned))
+    with ThreadPoolExecutor(max_workers=min(8, max(1, len(doms)))) as ex:
+        for idx, val in ex.map(rhs_part, doms):
+            b[idx] = val
     return n, nb, spg, doms, plan, b
 
 
@@ -401,12 +440,16 @@ def one_rank_of(args):
     pc.set_sizes(nloc, 1)
     pc.add_subdomain(0, np.arange(nloc), dom.mult, dom.a_neu, dom.a_dir)
     bd = DeviceVector.from_host(lib, b)
+    kept = {}
 
-    def step():
+    def step(keep=False):
         pc.setup(bd)
         x, its, rnorm, reason = pc.solve(bd)
         info = pc.info()
-        x.free()
+        if keep:        # --dump-outputs: the last timed step's solution stays on the device until it is written
+            kept.update(x=x, rnorm=rnorm)
+        else:
+            x.free()
         return its, reason, info
 
     cold_t0 = time.perf_counter()
@@ -420,8 +463,8 @@ def one_rank_of(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     last = None
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        last = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lib.GeneoKernelProfileStop()
@@ -432,10 +475,16 @@ def one_rank_of(args):
     nsamp, nlaunch = C.c_longlong(0), C.c_longlong(0)
     lib.GeneoKernelProfileGet(0, C.byref(ms_sum), C.byref(by_sum), None, C.byref(nsamp), C.byref(nlaunch))
     gbs = by_sum.value / max(ms_sum.value, 1e-9) * 1e-6
-    pc.setup(bd)                        # untimed step with the in-situ timer off (inner PCG chunks replay as HIP graphs)
-    xg, gits, _, _ = pc.solve(bd)
-    ginfo = pc.info()
-    xg.free()
+    if args.dump_outputs is not None:
+        xk = kept.pop("x")
+        dump_outputs(args.dump_outputs, xk.to_host(), np.arange(nloc), its, kept["rnorm"], info["dimE"],
+                     pc.residual_history(), pc.local_dims())
+        xk.free()
+    if args.full:
+        pc.setup(bd)                    # untimed step with the in-situ timer off (inner PCG chunks replay as HIP graphs)
+        xg, gits, _, _ = pc.solve(bd)
+        ginfo = pc.info()
+        xg.free()
     dom_k = max(kernels, key=lambda k: k["share_of_step"]) if kernels else None
     roof = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "traffic": None,
             "kernel": "k_spmv_sell"}
@@ -471,11 +520,12 @@ def one_rank_of(args):
         "amg_levels": info["amg_levels"], "amg_setup_s": info["amgSetupTime"], "host_prep_s": prep_s,
         "setup_breakdown_s": {"level1_upload_and_amg": info["lvl1SetupMinvTimeLoc"],
                               "eigensolve_lobpcg": info["lvl2SetupEigTimeLoc"], "coarse_operator_E": info["lvl2SetupETimeLoc"]},
-        "untimed_step_with_hip_graphs_s": {"setup": ginfo["setupTime"], "solve": ginfo["solveTime"], "iterations": gits},
         "solve_breakdown_s": {"local_solves": info["lvl1ApplyMinvTimeLoc"], "coarse_Zt": info["lvl2ApplyZtTimeLoc"],
                               "coarse_Einv": info["lvl2ApplyEinvTimeLoc"]},
         "roofline": roof,
     }
+    if args.full:
+        out["untimed_step_with_hip_graphs_s"] = {"setup": ginfo["setupTime"], "solve": ginfo["solveTime"], "iterations": gits}
     out["bench_wall_s"] = round(time.perf_counter() - T_PROCESS0, 1)
     print(json.dumps(out), flush=True)
     pc.destroy()
@@ -678,11 +728,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def step():
+    kept = {}
+
+    def step(keep=False):
         pc.setup(bd)
         x, its, rnorm, reason = pc.solve(bd)
         info = pc.info()
-        x.free()
+        if keep:        # --dump-outputs: the last timed step's solution stays on the device until it is written
+            kept.update(x=x, rnorm=rnorm)
+        else:
+            x.free()
         return its, reason, info
 
     first_setup = None
@@ -700,8 +755,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     last = None
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        last = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     barrier()
     elapsed = time.perf_counter() - t0
     lib.GeneoKernelProfileStop()
@@ -711,23 +766,31 @@ def main():
     ms_sum, by_sum = C.c_double(0), C.c_double(0)
     nsamp, nlaunch = C.c_longlong(0), C.c_longlong(0)
     lib.GeneoKernelProfileGet(0, C.byref(ms_sum), C.byref(by_sum), None, C.byref(nsamp), C.byref(nlaunch))
-    # One more, UNTIMED step with the in-situ timer off: the inner PCG chunks then replay as HIP graphs (the timer
-    # needs direct launches: HIP events cannot bracket kernels inside a graph), which is how the library runs
-    # outside this benchmark.  Reported as information only.
-    pc.setup(bd)
-    xg, gits, _, greason = pc.solve(bd)
-    ginfo = pc.info()
-    # true residual || A x - b || / || b || of that solve (driver:1072-1087), owned rows, summed over the ranks
-    axg = pc.matmult(xg)
-    rr = axg.to_host() - b
-    num, den = float(rr @ rr), float(b @ b)
-    xg.free()
-    axg.free()
-    if dist is not None:
-        tt = torch.tensor([num, den], device=red_dev, dtype=torch.float64)
-        dist.all_reduce(tt)
-        num, den = float(tt[0]), float(tt[1])
-    true_res = (num / den) ** 0.5
+    if args.dump_outputs is not None:
+        xk = kept.pop("x")
+        if rank == 0:
+            dump_outputs(args.dump_outputs, xk.to_host(), plan.owned, its, kept["rnorm"], info["dimE"],
+                         pc.residual_history(), pc.local_dims())
+        xk.free()
+    ginfo, gits, true_res = None, None, None
+    if args.full:
+        # One more, UNTIMED step with the in-situ timer off: the inner PCG chunks then replay as HIP graphs (the timer
+        # needs direct launches: HIP events cannot bracket kernels inside a graph), which is how the library runs
+        # outside this benchmark.  Reported as information only.
+        pc.setup(bd)
+        xg, gits, _, greason = pc.solve(bd)
+        ginfo = pc.info()
+        # true residual || A x - b || / || b || of that solve (driver:1072-1087), owned rows, summed over the ranks
+        axg = pc.matmult(xg)
+        rr = axg.to_host() - b
+        num, den = float(rr @ rr), float(b @ b)
+        xg.free()
+        axg.free()
+        if dist is not None:
+            tt = torch.tensor([num, den], device=red_dev, dtype=torch.float64)
+            dist.all_reduce(tt)
+            num, den = float(tt[0]), float(tt[1])
+        true_res = (num / den) ** 0.5
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed, info["setupTime"], info["solveTime"]], device=red_dev, dtype=torch.float64)
@@ -754,45 +817,47 @@ def main():
         # algorithmic bytes per launch.
         # The file names the kernel source it was measured on (sha256 of csrc/backend_hip.hip): a profile older than the
         # kernels is NOT applied -- traffic stays null and the line says why.
-        traffic_note = None
-        try:
-            import hashlib
-            pmc_path = os.path.join(ROOT, "profiles", "r04_hbm_traffic_pmc.json")
-            prof = json.load(open(pmc_path))
-            sha = hashlib.sha256(open(os.path.join(ROOT, "geneo4petsc_amd", "csrc", "backend_hip.hip"), "rb").read()).hexdigest()[:16]
-            if prof.get("kernel_source_sha16") != sha:
-                traffic_note = ("profiles/r04_hbm_traffic_pmc.json was measured on kernel source %s, this is %s: stale, not applied"
-                                % (prof.get("kernel_source_sha16"), sha))
-                print("bench.py: " + traffic_note, file=sys.stderr, flush=True)
-                prof = {}
-            for k in kernels:
-                key = k["kernel"].split(" ")[0]
-                hits = [v for name, v in prof.items() if isinstance(v, dict) and (name == key or name.startswith(key + "<") or name.startswith(key + "_ld"))
-                        and "traffic_over_algorithmic" in v]
-                hits.sort(key=lambda v: -v["traffic_over_algorithmic"])      # several forms of a class measured: the worst ratio
-                # the ratio of a class is a property of the matrix the XCDs walk: applied when the profile was measured on
-                # this rank's rows or on ONE of its (equal) subdomains
-                prow = hits[0].get("rows", info_rows) if hits else 0
-                if hits and (abs(prow - info_rows) <= 0.01 * info_rows or abs(prow - info_rows / max(1, len(doms))) <= 0.01 * prow):
-                    k["traffic_over_algorithmic"] = hits[0]["traffic_over_algorithmic"]
-                    k["traffic"] = hits[0]["traffic_over_algorithmic"] * k["algorithmic_bytes_per_launch"]
-        except Exception as e:
-            traffic_note = "no PMC profile applied: %r" % (e,)
-        # MFMA utilisation of the Rayleigh-Ritz kernels (north_star: "MFMA utilisation for the Rayleigh-Ritz step"): PMC
-        # passes of scripts/pmc.py (scripts/gpu.sh pmcm), attached to the two MFMA rows under the same staleness rule
-        try:
-            mp = json.load(open(os.path.join(ROOT, "profiles", "r04_mfma_pmc.json")))
-            if mp.get("kernel_source_sha16") == sha:
+        traffic_note = "PMC traffic and MFMA utilisation from profiles/ are attached by bench.py --full"
+        if args.full:
+            traffic_note = None
+            try:
+                import hashlib
+                pmc_path = os.path.join(ROOT, "profiles", "r04_hbm_traffic_pmc.json")
+                prof = json.load(open(pmc_path))
+                sha = hashlib.sha256(open(os.path.join(ROOT, "geneo4petsc_amd", "csrc", "backend_hip.hip"), "rb").read()).hexdigest()[:16]
+                if prof.get("kernel_source_sha16") != sha:
+                    traffic_note = ("profiles/r04_hbm_traffic_pmc.json was measured on kernel source %s, this is %s: stale, not applied"
+                                    % (prof.get("kernel_source_sha16"), sha))
+                    print("bench.py: " + traffic_note, file=sys.stderr, flush=True)
+                    prof = {}
                 for k in kernels:
                     key = k["kernel"].split(" ")[0]
-                    hits = {name: v for name, v in mp.items() if isinstance(v, dict) and name.startswith(key) and "MfmaUtil" in v}
-                    if hits:
-                        k["mfma_util_percent"] = {name: v["MfmaUtil"] for name, v in hits.items()}
-                        k["mfma_util_source"] = "profiles/r04_mfma_pmc.json (rocprofv3 --pmc MfmaUtil, same kernel source)"
-            elif rank == 0:
-                print("bench.py: profiles/r04_mfma_pmc.json is older than the kernels: MFMA utilisation not attached", file=sys.stderr, flush=True)
-        except Exception:
-            pass
+                    hits = [v for name, v in prof.items() if isinstance(v, dict) and (name == key or name.startswith(key + "<") or name.startswith(key + "_ld"))
+                            and "traffic_over_algorithmic" in v]
+                    hits.sort(key=lambda v: -v["traffic_over_algorithmic"])      # several forms of a class measured: the worst ratio
+                    # the ratio of a class is a property of the matrix the XCDs walk: applied when the profile was measured on
+                    # this rank's rows or on ONE of its (equal) subdomains
+                    prow = hits[0].get("rows", info_rows) if hits else 0
+                    if hits and (abs(prow - info_rows) <= 0.01 * info_rows or abs(prow - info_rows / max(1, len(doms))) <= 0.01 * prow):
+                        k["traffic_over_algorithmic"] = hits[0]["traffic_over_algorithmic"]
+                        k["traffic"] = hits[0]["traffic_over_algorithmic"] * k["algorithmic_bytes_per_launch"]
+            except Exception as e:
+                traffic_note = "no PMC profile applied: %r" % (e,)
+            # MFMA utilisation of the Rayleigh-Ritz kernels (north_star: "MFMA utilisation for the Rayleigh-Ritz step"): PMC
+            # passes of scripts/pmc.py (scripts/gpu.sh pmcm), attached to the two MFMA rows under the same staleness rule
+            try:
+                mp = json.load(open(os.path.join(ROOT, "profiles", "r04_mfma_pmc.json")))
+                if mp.get("kernel_source_sha16") == sha:
+                    for k in kernels:
+                        key = k["kernel"].split(" ")[0]
+                        hits = {name: v for name, v in mp.items() if isinstance(v, dict) and name.startswith(key) and "MfmaUtil" in v}
+                        if hits:
+                            k["mfma_util_percent"] = {name: v["MfmaUtil"] for name, v in hits.items()}
+                            k["mfma_util_source"] = "profiles/r04_mfma_pmc.json (rocprofv3 --pmc MfmaUtil, same kernel source)"
+                elif rank == 0:
+                    print("bench.py: profiles/r04_mfma_pmc.json is older than the kernels: MFMA utilisation not attached", file=sys.stderr, flush=True)
+            except Exception:
+                pass
         dom = max(kernels, key=lambda k: k["share_of_step"]) if kernels else None
         roof = {"bound": "hbm", "achieved": gbs_rank, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs_rank / HBM_PEAK_GBS,
                 "traffic": None, "kernel": "k_spmv_sell"}
@@ -847,18 +912,19 @@ def main():
             "setup_breakdown_s": {"level1_upload_and_amg": info["lvl1SetupMinvTimeLoc"],
                                   "eigensolve_lobpcg": info["lvl2SetupEigTimeLoc"],
                                   "coarse_operator_E": info["lvl2SetupETimeLoc"]},
-            "untimed_step_with_hip_graphs_s": {"setup": ginfo["setupTime"], "solve": ginfo["solveTime"],
-                                               "iterations": gits, "true_residual": true_res},
             "solve_breakdown_s": {"local_solves": info["lvl1ApplyMinvTimeLoc"], "coarse_Zt": info["lvl2ApplyZtTimeLoc"],
                                   "coarse_Einv": info["lvl2ApplyEinvTimeLoc"]},
             "roofline": roof,
         }
+        if args.full:
+            out["untimed_step_with_hip_graphs_s"] = {"setup": ginfo["setupTime"], "solve": ginfo["solveTime"],
+                                                     "iterations": gits, "true_residual": true_res}
         # the oracle's counts at THIS grid, when a golden holds them (tests/golden/headline.json: 96^3, 126^3 at these options)
         try:
             gold = json.load(open(os.path.join(ROOT, "tests", "golden", "headline.json"))).get(str(n), {}).get("literal")
             default_opts = (args.workload == "laplacian" and nb == 8 and args.lvl == "SRAS,1" and args.cut == 20 and args.tau == 0.35
                             and args.eps_tol == 1e-3 and args.rtol == 1e-5 and args.overlap == 2 and not args.pc_args)
-            if gold and default_opts:
+            if gold and default_opts and args.full:
                 spread = sorted(set([gold["cg"]["its"]] + [c for v in gold.get("cg_spread", {}).values() for c in v]))
                 out["golden_at_this_grid"] = {"source": "tests/golden/headline.json (reference-literal oracle: exact LU, ARPACK at 1e-3)",
                                               "oracle_pcg_iterations": gold["cg"]["its"], "oracle_pcg_spread_under_perturbation": spread,
@@ -869,7 +935,7 @@ def main():
                                               "pcg_count_inside_oracle_spread": bool(min(spread) <= int(its) <= max(spread))}
         except Exception:
             pass
-        if args.workload == "heat":
+        if args.workload == "heat" and args.full:
             # configs[3]: the same problem with plain one-level ASM (-geneo_lvl ASM,0), PCG iteration counts side by side
             pc0 = GenEOPC(lib)
             pc0.set_from_options([a if a != args.lvl else "ASM,0" for a in argv] + ["-ksp_max_it", "5000"])
@@ -884,7 +950,7 @@ def main():
             out["asm0_vs_geneo"] = {"ASM,0": {"iterations": int(its0), "converged": reason0, "setup_s": i0["setupTime"], "solve_s": i0["solveTime"]},
                                     args.lvl: {"iterations": int(its), "converged": reason, "dimE": info["dimE"],
                                                "setup_s": setup_s, "solve_s": solve_s}}
-        if size == 1 and not args.no_cpu_baseline and args.workload == "laplacian":
+        if size == 1 and args.full and not args.no_cpu_baseline and args.workload == "laplacian":
             if spmv_ws <= 256 * 2 ** 20:     # only where the in-situ rate is cache-assisted
                 try:
                     roof["spmv_hbm_resident"] = spmv_hbm_resident(lib, doms)
@@ -896,7 +962,7 @@ def main():
                 out["parity_sample"] = out["cpu_baseline"].pop("parity_sample")
     pc.destroy()
     if rank == 0:
-        if size > 1 and not args.no_anchor and args.scaling == "weak":
+        if size > 1 and args.full and not args.no_anchor and args.scaling == "weak":
             # The weak-scaling curve compares N GPUs x (184^3, ONE subdomain each) with ... what on one GPU?  bench.py's N = 1
             # line is 126^3 in 8 subdomains (BASELINE configs[1]); the like-for-like anchor -- the SAME per-GPU DoF count on
             # one GPU, where the two-level method needs several subdomains -- is 184^3 in 8 subdomains, run here on rank 0's

@@ -11,7 +11,7 @@ f3=lambda v: "%.2f"%v
 N['S368']=f3(d['setup_s']); N['V368']=f3(d['solve_s']); N['MS368']="%.2f"%(d['ms_per_step']/1e3); N['MEM368']="%.0f"%d['device_mem_peak_gb']
 N['FOOT368']="%.0f"%d['device_memory']['device_mem_footprint_peak_gb']
 N['COLD368']="%.1f"%d['first_setup_s']['setup']; N['PREP368']="%.1f"%d['host_prep_s']
-N['WALL368']=open(ROOT+"/gpurun_out/driverlike_wall.txt").read().split('wall')[1].split()[0]
+N['WALL368']=open(os.path.join(ROOT, os.environ.get("OUT_DIR", "bench_out"), "driverlike_wall.txt")).read().split('wall')[1].split()[0]   # scripts/dev/final_default.sh
 sb=d['setup_breakdown_s']; N['L1368']=f3(sb['level1_upload_and_amg'])+" s"; N['EIG368']=f3(sb['eigensolve_lobpcg'])+" s"; N['E368']=f3(sb['coarse_operator_E'])+" s"
 so=d['solve_breakdown_s']; N['LS368']=f3(so['local_solves']); N['CZ368']="%.4f"%(so['coarse_Zt']+so['coarse_Einv'])
 N['INNER368']=str(d['local_solve_cg_iterations'])

@@ -44,3 +44,25 @@ def test_one_rank_of_8_flags_parse():
     assert args.one_rank_of == 8 and args.rank_index == 7 and args.apply_count == 5
     with pytest.raises(SystemExit):
         bench.build_parser().parse_args(["--one-rank-of", "4"])
+
+
+def test_plain_run_is_lean_and_dump_outputs_are_reproducible(tmp_path):
+    """A plain bench line does no extra legs (--full is off by default); --dump-outputs writes float64 .npy files, at most
+    64 MB in all, the same sampled rows for the same problem size."""
+    args = bench.build_parser().parse_args(["--steps", "3"])
+    assert args.steps == 3 and not args.full and args.dump_outputs is None
+    assert bench.build_parser().parse_args(["--full", "--dump-outputs", "d"]).full
+    n = bench.DUMP_X_ROWS + 1000
+    x = np.arange(n, dtype=np.float64) * 0.5
+    runs = []
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), x, np.arange(n) + 3, 25, 1e-3, 160, np.ones(26), np.full(8, 20, dtype=np.int32))
+        files = sorted(p.name for p in (tmp_path / sub).iterdir())
+        assert sum((tmp_path / sub / f).stat().st_size for f in files) <= 64 * 2 ** 20
+        runs.append({f[:-4]: np.load(tmp_path / sub / f) for f in files})
+    a, b = runs
+    assert set(a) == {"x", "x_index", "residual_history", "local_dims", "iterations", "rnorm", "dimE"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert len(a["x"]) == bench.DUMP_X_ROWS and np.array_equal(a["x"], (a["x_index"] - 3) * 0.5)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["iterations"][0] == 25 and a["dimE"][0] == 160

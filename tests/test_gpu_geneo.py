@@ -21,13 +21,22 @@ def lib():
     return _lib.load()
 
 
+# The oracle's OWN PCG count of one mode case depends on the host it runs on: SRAS,1 / CG / overlap 2 meets rtol 1e-6 at
+# iteration 24 or 25, and which one is decided by the summation order of the host's BLAS (OpenBLAS picks its kernels by
+# CPU model and splits its loops by thread count): 24 with the Haswell or Zen kernels on one thread (iteration 23 at 1.17
+# of the threshold), 25 with the SkylakeX or Sandybridge kernels or several threads.  The GPU's 25 is one of the oracle's
+# own answers; this one pair is declared (cases.compare_with_oracle still compares the first residual norms to 1e-8 and
+# records the case in cases.COUNT_DRIFT, printed in the terminal summary).  Every other count stays exact.
+HOST_BLAS_DRIFT = {("SRAS,1", "cg", 2): [(25, 24)]}
+
+
 @pytest.mark.parametrize("lvl,ksp,overlap", [("ASM,0", "cg", 1), ("ASM,1", "cg", 1), ("ASM,1", "gmres", 2),
                                              ("RAS,1", "gmres", 1), ("SRAS,1", "cg", 2), ("ASM,H1", "cg", 1),
                                              ("ASM,E1", "gmres", 1), ("SRAS,H1", "cg", 2), ("SRAS,1", "cg", 1),
                                              ("RAS,H1", "gmres", 2), ("ORAS,1", "gmres", 1)])
 def test_modes_match_oracle(lib, lvl, ksp, overlap):
     argv = ["-geneo_lvl", lvl, "-geneo_tau", "0.2", "-geneo_cut", "8", "-ksp_type", ksp] + TIGHT
-    cases.compare_with_oracle(lib, 12, (2, 2, 2), overlap, argv)
+    cases.compare_with_oracle(lib, 12, (2, 2, 2), overlap, argv, count_drift=HOST_BLAS_DRIFT.get((lvl, ksp, overlap)))
 
 
 @pytest.mark.parametrize("lvl,ksp,n,parts,cut,inter", [("SORAS,2", "cg", 12, (3, 2, 1), 12, True),
@@ -316,11 +325,12 @@ def test_cooperative_reductions_of_large_subdomains(lib, lvl, ksp, overlap):
     Forced here on small cases (threshold 0): full parity with the oracle, and the same counts as the default forms."""
     argv = ["-geneo_lvl", lvl, "-geneo_tau", "0.2", "-geneo_cut", "8", "-ksp_type", ksp] + TIGHT
     n, parts = 12, (2, 2, 2)          # the cases of test_modes_match_oracle
-    its_default, info_default = cases.compare_with_oracle(lib, n, parts, overlap, argv)
+    drift = HOST_BLAS_DRIFT.get((lvl, ksp, overlap))
+    its_default, info_default = cases.compare_with_oracle(lib, n, parts, overlap, argv, count_drift=drift)
     old = lib.GeneoSetParReduceMin(0)
     try:
         assert lib.GeneoSetParReduceMin(0) == 0
-        its, info = cases.compare_with_oracle(lib, n, parts, overlap, argv)
+        its, info = cases.compare_with_oracle(lib, n, parts, overlap, argv, count_drift=drift)
     finally:
         lib.GeneoSetParReduceMin(old)
     assert its == its_default and info["dimE"] == info_default["dimE"]
