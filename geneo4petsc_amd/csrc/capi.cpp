@@ -798,4 +798,185 @@ PetscErrorCode GeneoBlockKernel(int kind, int nsub, const int* suboff, const dou
   return 0;
 }
 
+// ---- test hooks of the backend primitives (tests/primitive_cases.py) ---------------------------------------------------
+// No arithmetic here: arguments are unpacked, bk:: is called, results stay where the primitive wrote them.  Every pointer
+// in parg is a device pointer of the caller (GeneoDeviceAlloc) except parg[0] of the chunked primitives: the HOST array
+// suboff (iarg[0] = nsub), from which the bk::Chunks is built around the call.
+// Returns the primitive's own result (void: 0, bool: 0 / 1, recip_positive: its count), -1 on an exception (message:
+// PCGenEOGetError(NULL)), -2 for an unknown name.
+int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* const* P) {
+  const std::string k(name ? name : "");
+  auto d = [&](int i) { return (double*)P[i]; };
+  auto ip = [&](int i) { return (int*)P[i]; };
+  auto lp = [&](int i) { return (int64_t*)P[i]; };
+  bk::Chunks c;
+  bool have_chunks = false;
+  int rc = 0;
+  try {
+    // ---- plain vectors and blocks
+    if (k == "gather") bk::gather(d(0), d(1), ip(2), I[0]);
+    else if (k == "gather_mul") bk::gather_mul(d(0), d(1), ip(2), d(3), I[0]);
+    else if (k == "segsum") bk::segsum(d(0), d(1), ip(2), ip(3), I[0], I[1] != 0);
+    else if (k == "gather_rows") bk::gather_rows(d(0), d(1), ip(2), I[0], I[1]);
+    else if (k == "segsum_rows") bk::segsum_rows(d(0), d(1), ip(2), ip(3), I[0], I[1], I[2] != 0);
+    else if (k == "set") bk::set(d(0), D[0], I[0]);
+    else if (k == "zero") bk::zero(P[0], (size_t)I[0]);
+    else if (k == "copy") bk::copy(d(0), d(1), I[0]);
+    else if (k == "axpy") bk::axpy(d(0), D[0], d(1), I[0]);
+    else if (k == "axpby") bk::axpby(d(0), D[0], d(1), D[1], I[0]);
+    else if (k == "xmy") bk::xmy(d(0), d(1), d(2), I[0]);
+    else if (k == "axpy_dev") bk::axpy_dev(d(0), d(1), D[0], d(2), I[0]);
+    else if (k == "dot") bk::dot(d(0), d(1), I[0], d(2));
+    else if (k == "block_axpby") bk::block_axpby(d(0), I[0], D[0], d(1), I[1], D[1], I[2], I[3]);
+    else if (k == "block_rowscale") bk::block_rowscale(d(0), I[0], d(1), I[1], d(2), D[0], D[1], I[2], I[3]);
+    else if (k == "jacobi_step") bk::jacobi_step(d(0), I[0], d(1), I[1], d(2), d(3), D[0], I[2], I[3], I[4] != 0);
+    else if (k == "cheb_update") bk::cheb_update(d(0), d(1), d(2), d(3), I[0], d(4), D[0], D[1], I[1], I[2]);
+    else if (k == "chol_solve") rc = bk::chol_solve(d(0), d(1), I[0], d(2)) ? 1 : 0;
+    else if (k == "recip_positive") rc = bk::recip_positive(d(0), I[0]);
+    else {
+      // ---- chunked primitives
+      c = bk::chunks_upload(I[0], (const int*)P[0]);
+      have_chunks = true;
+      if (k == "seg_dot") bk::seg_dot(c, d(1), d(2), d(3), I[1], I[2]);
+      else if (k == "dense_sym_apply") bk::dense_sym_apply(c, d(1), lp(2), d(3), I[1], d(4), I[2], I[3]);
+      else if (k == "gram") bk::gram(c, d(1), I[1], I[2], d(2), I[3], I[4], d(3));
+      else if (k == "block_mul") bk::block_mul(c, d(1), I[1], I[2], d(2), I[3], d(3), I[4], I[5] != 0);
+      else if (k == "block_residual") bk::block_residual(c, d(1), I[1], d(2), I[2], d(3), I[3], d(4), I[4], d(5));
+      else if (k == "block_colnorm") bk::block_colnorm(c, d(1), I[1], I[2], d(2));
+      else if (k == "block_residual_norms")
+        bk::block_residual_norms(c, d(1), I[1], d(2), I[2], d(3), I[3], d(4), I[4], d(5), d(6));
+      else if (k == "block_colscale") bk::block_colscale(c, d(1), I[1], I[2], d(2));
+      else if (k == "block_init")
+        bk::block_init(c, d(1), I[1], I[2], ip(2), ((uint64_t)(uint32_t)I[4] << 32) | (uint64_t)(uint32_t)I[3]);
+      else if (k == "block_extract") bk::block_extract(c, d(1), I[1], I[2], d(2), ip(3), ip(4), lp(5), d(6));
+      else if (k == "z_rowmajor") bk::z_rowmajor(c, d(1), lp(2), ip(3), d(4), I[1]);
+      else if (k == "zt_apply") bk::zt_apply(c, d(1), lp(2), ip(3), ip(4), I[1], d(5), d(6), I[2]);
+      else if (k == "z_apply") bk::z_apply(c, d(1), lp(2), ip(3), ip(4), d(5), d(6), I[1] != 0);
+      else rc = -2;
+    }
+    bk::sync();
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    rc = -1;
+  }
+  if (have_chunks) bk::chunks_free(c);
+  return rc;
+}
+
+// The batched CG of the local solves on the matrix of `h` (rows 0 .. suboff[nsub]): cg_start, then `iters` times
+// [spmv, seg_pap, cg_update, cg_direction] with alternating parity, ONE bk::Chunks alive across the sequence (it carries
+// the chunk partials).  caller_precond != 0: the caller-preconditioned form -- cg_start / cg_update with dinv == nullptr,
+// z = dinv .* r by bk::xmy, seg_partial(r, z, 1), cg_set_rz and p = z after the start (the order of PC::local_solve).
+// x, r, z, p, b, dinv: device vectors; sc_out: host, nsub x 8.
+PetscErrorCode GeneoTestCgSteps(GeneoSpmv h, int nsub, const int* suboff, int iters, double tol2, int caller_precond,
+                                const double* b, const double* dinv, double* x, double* r, double* z, double* p,
+                                double* sc_out) {
+  if (!h) return 1;
+  GUARD_BEGIN
+  const int n = suboff[nsub], n0 = suboff[0];
+  bk::Chunks c = bk::chunks_upload(nsub, suboff);
+  double* sc = (double*)bk::alloc(sizeof(double) * 8 * (size_t)std::max(1, nsub));
+  double* q = (double*)bk::alloc(sizeof(double) * (size_t)std::max(1, n));
+  const double* dv = caller_precond ? nullptr : dinv;
+  bk::cg_start(c, sc, x, r, z, p, b, dv);
+  if (caller_precond) {
+    bk::xmy(z + n0, r + n0, dinv + n0, n - n0);
+    bk::seg_partial(c, r, z, 1);
+    bk::cg_set_rz(c, sc);
+    bk::copy(p + n0, z + n0, n - n0);
+  }
+  int parity = 0;
+  for (int it = 0; it < iters; ++it) {
+    bk::spmv(h->a, p, q);
+    bk::seg_pap(c, p, q);
+    bk::cg_update(c, sc, parity, x, r, z, p, q, dv);
+    if (caller_precond) {
+      bk::xmy(z + n0, r + n0, dinv + n0, n - n0);
+      bk::seg_partial(c, r, z, 1);
+    }
+    bk::cg_direction(c, sc, parity, p, z, tol2);
+    parity ^= 1;
+  }
+  bk::d2h(sc_out, sc, sizeof(double) * 8 * (size_t)nsub);
+  bk::dfree(sc);
+  bk::dfree(q);
+  bk::chunks_free(c);
+  GUARD_END((PC) nullptr)
+  return 0;
+}
+
+// Set-up operations on CSR matrices (host CSR in, host CSR out; parg: device arrays of the caller).  Returns the number of
+// entries of the result and fills the outputs when cap allows (as GeneoTestSparseProduct), -1: a sparse product exceeded
+// the kernels' capacity, -2: error, -3: post_matrix returned false.
+//   op 0  csr_remap_columns(A, parg[0])
+//   op 1  csr_scaled_alias(A, parg[0], parg[1], iarg[0]); iarg[1] = m > 0: then spmm_fused(alias, EPI_PRE) with
+//         Y = parg[2] (ld iarg[2]), B = parg[3] (ld iarg[3]), Z = parg[4] (ld iarg[4]; may be null), dinv = parg[5], w = darg[0]
+//   op 2  csr_tentative_prolongator(A.n, agg = parg[0]); iarg[1] != 0: spgemm(A, P0, iarg[0] aggregates) and
+//         smooth_prolongator(., agg, dinv = parg[1], w = darg[0])
+//   op 3  post_matrix(AP = A, P = B, dinv = parg[0], w = darg[0])
+//   op 4  csr_diag(A, parg[0])                                    (returns nnz(A), no CSR output)
+//   op 5  C = spgemm(A, B, iarg[0]); csr_finish(C); spmv(C, parg[0], parg[1])
+long long GeneoTestCsrOp(int op, const GeneoCsr* A, const GeneoCsr* B, const int* iarg, const double* darg,
+                         void* const* parg, int* rowptr_out, int* col_out, double* val_out, long long cap) {
+  try {
+    const bool layouts = (op == 0 || op == 1);   // the SpMV layouts travel with these two
+    bk::Csr a = layouts ? bk::csr_upload(A->n, A->rowptr, A->col, A->val) : bk::csr_upload_raw(A->n, A->rowptr, A->col, A->val);
+    bk::Csr b, c;
+    long long nnz = -2;
+    auto out = [&](const bk::Csr& m) {
+      nnz = (long long)m.nnz;
+      if (cap >= nnz && rowptr_out) bk::csr_download(m, rowptr_out, col_out, val_out);
+    };
+    if (op == 0) {
+      c = bk::csr_remap_columns(a, (const int*)parg[0]);
+      out(c);
+      bk::csr_free(c);
+    } else if (op == 1) {
+      c = bk::csr_scaled_alias(a, (const double*)parg[0], (const double*)parg[1], iarg[0] != 0);
+      if (iarg[1] > 0)
+        bk::spmm_fused(c, bk::EPI_PRE, nullptr, 0, (double*)parg[2], iarg[2], iarg[1], (const double*)parg[3], iarg[3],
+                       (double*)parg[4], iarg[4], (const double*)parg[5], darg[0]);
+      out(c);
+      bk::csr_free(c);
+    } else if (op == 2) {
+      b = bk::csr_tentative_prolongator(A->n, (const int*)parg[0]);
+      if (iarg[1]) {
+        bool ok = true;
+        c = bk::spgemm(a, b, iarg[0], &ok);
+        if (ok) {
+          bk::smooth_prolongator(c, (const int*)parg[0], (const double*)parg[1], darg[0]);
+          out(c);
+          bk::csr_free(c);
+        } else nnz = -1;
+      } else out(b);
+      bk::csr_free(b);
+    } else if (op == 3) {
+      b = bk::csr_upload_raw(B->n, B->rowptr, B->col, B->val);
+      if (bk::post_matrix(a, b, (const double*)parg[0], darg[0])) out(a);
+      else nnz = -3;
+      bk::csr_free(b);
+    } else if (op == 4) {
+      bk::csr_diag(a, (double*)parg[0]);
+      nnz = (long long)a.nnz;
+    } else if (op == 5) {
+      b = bk::csr_upload_raw(B->n, B->rowptr, B->col, B->val);
+      bool ok = true;
+      c = bk::spgemm(a, b, iarg[0], &ok);
+      if (ok) {
+        bk::csr_finish(c);
+        bk::spmv(c, (const double*)parg[0], (double*)parg[1]);
+        out(c);
+        bk::csr_free(c);
+      } else nnz = -1;
+      bk::csr_free(b);
+    }
+    bk::sync();
+    bk::csr_free(a);
+    return nnz;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -2;
+  }
+}
+
 }  // extern "C"

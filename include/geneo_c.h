@@ -373,6 +373,25 @@ PetscErrorCode GeneoTestLobpcgUpdate(int nsub, const int* suboff, const double* 
                                      const double* C, const double* keep, const double* lam, const double* mask,
                                      double* T, double* AT, double* BT, double* R);
 
+/* Test hooks of the backend primitives (csrc/backend.h), one call each, on device pointers of the caller
+ * (GeneoDeviceAlloc / GeneoH2D); the argument layout per primitive name is tabulated in tests/primitive_cases.py.
+ * Chunked primitives take iarg[0] = nsub and parg[0] = the HOST array suboff (nsub + 1 absolute first rows).
+ * Returns the primitive's own result (void: 0, bool: 0 / 1, recip_positive: its count), -1 on an error
+ * (PCGenEOGetError(NULL)), -2 for an unknown name. */
+int GeneoTestPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
+/* cg_start and `iters` steps [spmv, seg_pap, cg_update, cg_direction] of the batched CG on the matrix of `h`
+ * (suboff[nsub] rows) with one chunk list alive across the sequence; caller_precond != 0: the form with dinv == NULL in
+ * cg_start / cg_update (z = dinv .* r by xmy, seg_partial(r, z, 1), cg_set_rz).  Device vectors; sc_out: host, nsub x 8. */
+PetscErrorCode GeneoTestCgSteps(GeneoSpmv h, int nsub, const int* suboff, int iters, double tol2, int caller_precond,
+                                const double* b_dev, const double* dinv_dev, double* x_dev, double* r_dev, double* z_dev,
+                                double* p_dev, double* sc_out);
+/* multigrid set-up operations on CSR (host CSR in and out, device arrays in parg); op 0 csr_remap_columns, 1
+ * csr_scaled_alias (+ spmm_fused EPI_PRE), 2 csr_tentative_prolongator (+ spgemm + smooth_prolongator), 3 post_matrix,
+ * 4 csr_diag, 5 spgemm + csr_finish + spmv.  Returns nnz of the result (outputs filled when cap >= nnz), -1: product
+ * over capacity, -2: error, -3: post_matrix returned false. */
+long long GeneoTestCsrOp(int op, const GeneoCsr* A, const GeneoCsr* B, const int* iarg, const double* darg,
+                         void* const* parg, int* rowptr_out, int* col_out, double* val_out, long long cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -568,6 +568,8 @@ void block_residual(const Chunks& c, const double* AX, int lda, const double* BX
 }
 void block_residual_norms(const Chunks& c, const double* AX, int lda, const double* BX, int ldb, const double* lam,
                           int m, double* R, int ldr, const double* colmask, double* nrm3) {
+  if (c.nchunk == 0) return;
+  if (3 * m > 256) throw std::runtime_error("block_residual_norms: m > 85");   // as the HIP backend
   for (int s = 0; s < c.nsub; ++s)
     OMP_ROWS
     for (int j = 0; j < m; ++j) {
@@ -671,7 +673,7 @@ void block_extract(const Chunks& c, const double* X, int ldx, int m, const doubl
 }
 void zt_apply(const Chunks& c, const double* Z, const int64_t* zbase, const int* ksub, const int* zoff, int kmax,
               const double* xL, double* yE, int dimE_total) {
-  (void)kmax;
+  if (kmax > 256) throw std::runtime_error("zt_apply: more than 256 coarse vectors in one subdomain");   // as the HIP backend
   for (int e = 0; e < dimE_total; ++e) yE[e] = 0;
   for (int s = 0; s < c.nsub; ++s) {
     const int ns = c.suboff[s + 1] - c.suboff[s];
@@ -697,6 +699,7 @@ void set_mfma(bool) {}
 bool set_variant(const char*, int) { return false; }
 bool chol_solve(const double* L, const double* LT, int n, double* y) {   // the loops of dense::cholesky_solve_lu
   (void)LT;
+  if (n > 1024) return false;   // the capacity of the HIP kernel (one workgroup): the caller takes the host path
   for (int i = 0; i < n; ++i) {
     const double* li = L + (size_t)i * n;
     double s = y[i];

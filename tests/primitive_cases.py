@@ -1,0 +1,1128 @@
+"""Every primitive of csrc/backend.h called ALONE and compared with numpy, for any bound library: the HIP library
+(test_gpu_primitives.py) and the serial host twin (test_hostsim_primitives.py) run the same cases.
+
+Hooks: GeneoTestPrimitive (one primitive per call, arguments as tabulated in `_call` below), GeneoTestCgSteps (the
+batched CG sequence with its chunk partials alive across the steps), GeneoTestCsrOp (set-up operations on CSR).
+
+Techniques common to all cases
+  * canaries: every device buffer carries 64 doubles of a sentinel bit pattern in front and behind, padding columns
+    (ld - width) and rows no subdomain owns (suboff[0] != 0) hold the same pattern; all of it must come back
+    bit-unchanged.  Out-of-range and wrong-stride writes show up without a memory fault.
+  * determinism: primitives whose interface promises a fixed order run twice and must agree as uint64.
+  * inputs have magnitude in [0.5, 1.5) with random signs (fixed seeds): one missing or doubled term of a sum of n is
+    1/n of sum|terms|, far above every bound below.
+
+Bounds (u = 2^-53, references accumulated in np.longdouble)
+  * copies, gathers, one product (xmy, gather_mul, block_colscale, block_extract, csr_scaled_alias, z_rowmajor,
+    block_init): bit-exact -- an IEEE product or a copy leaves no freedom.
+  * a*x + b*y (axpy, axpby, axpy_dev, block_axpby): 2 u (|a x| + |b y|): two roundings on the longest path whether or
+    not the compiler contracts into an FMA.  Forms with more roundings on the path get that count instead of 2, on the
+    same sum of absolute terms: block_rowscale and the d-update of cheb_update 3 (a*d, *x, the sum), jacobi_step 4
+    (w*dinv, b - Ax, their product, the sum), post_matrix / smooth_prolongator 3.
+  * sums of n products in any order: n u sum|terms| (Higham, Accuracy and Stability, s. 3.1), n + 1 with `accumulate`.
+    Squared norms of a computed residual v = a - lam b add the propagated rounding of v:
+    sum(2 |v| e + e^2) with e = 2 u (|a| + |lam b|).
+  * chol_solve: componentwise backward error |L L^T x - b| <= 2 n u |L| |L^T| |x|.
+  * the CG sequence: rtol 1e-12 (the kernel-test convention of this project) relative to the scale of each vector /
+    of the subdomain's rr0, slot 6 (the active flag) exactly.
+"""
+import ctypes as C
+
+import numpy as np
+import scipy.sparse as sp
+
+from geneo4petsc_amd import _lib as L
+from geneo4petsc_amd.pc import Spmv, _csr_arrays, _csr_struct
+
+LD = np.longdouble
+U = 2.0 ** -53
+CHUNK = 1024
+SENT = np.uint64(0xC7D6E5F4A3B2C1D0)                  # a finite double (-2^126 or so): harmless if it is ever read
+SENTF = np.array([SENT], dtype=np.uint64).view(np.float64)[0]
+PAD = 512                                              # bytes of canary on each side = 64 doubles
+
+EPI_PRE = 4
+
+
+# ---------------------------------------------------------------------------------------------- plumbing
+class Buf:
+    """device copy of a host array between two canaries"""
+
+    def __init__(self, lib, host):
+        h = np.ascontiguousarray(host)
+        self.lib, self.shape, self.dtype, self.nbytes = lib, h.shape, h.dtype, h.nbytes
+        self.tot = PAD + ((h.nbytes + 7) // 8) * 8 + PAD
+        raw = np.full(self.tot // 8, SENT, dtype=np.uint64).view(np.uint8)
+        raw[PAD:PAD + h.nbytes] = h.reshape(-1).view(np.uint8)
+        self.base = lib.GeneoDeviceAlloc(self.tot)
+        assert self.base, "device allocation failed"
+        assert lib.GeneoH2D(self.base, raw.ctypes.data, self.tot) == 0
+        self.ptr = self.base + PAD
+
+    def get(self):
+        raw = np.empty(self.tot, dtype=np.uint8)
+        assert self.lib.GeneoD2H(raw.ctypes.data, self.base, self.tot) == 0
+        w = raw.view(np.uint64)
+        tail0 = (PAD + self.nbytes + 7) // 8
+        assert (w[:PAD // 8] == SENT).all(), "write in front of the buffer"
+        assert (w[tail0:] == SENT).all(), "write behind the buffer"
+        return raw[PAD:PAD + self.nbytes].view(self.dtype).reshape(self.shape).copy()
+
+    def free(self):
+        if self.base:
+            self.lib.GeneoDeviceFree(self.base)
+            self.base = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _ptr(p):
+    if p is None:
+        return None
+    if isinstance(p, Buf):
+        return p.ptr
+    return p.ctypes.data            # host array (suboff)
+
+
+def _call(lib, name, I=(), D=(), P=(), expect_error=False):
+    """GeneoTestPrimitive.  Arguments by name (I = iarg, D = darg, P = parg; chunked ones: I[0] = nsub, P[0] = suboff):
+      gather P(out,in,idx) I(n) | gather_mul P(out,in,idx,d) I(n) | segsum P(out,in,ptr,idx) I(nseg,acc)
+      gather_rows P(out,in,idx) I(n,w) | segsum_rows P(out,in,ptr,idx) I(nseg,w,acc)
+      set P(x) D(v) I(n) | zero P(x) I(bytes) | copy P(y,x) I(n) | axpy P(y,x) D(a) I(n) | axpby P(y,x) D(a,b) I(n)
+      xmy P(y,x,d) I(n) | axpy_dev P(y,a,x) D(sign) I(n) | dot P(x,y,out) I(n)
+      block_axpby P(Y,X) I(ldy,ldx,n,m) D(a,b) | block_rowscale P(Y,X,d) I(ldy,ldx,n,m) D(a,b)
+      jacobi_step P(X,B,AX,dinv) I(ldx,ldb,n,m,zero_guess) D(w) | cheb_update P(r,ad,d,z,dinv) I(ldz,n,m) D(a,b)
+      chol_solve P(L,LT,y) I(n) | recip_positive P(x) I(n)
+      seg_dot P(.,x,y,out) I(.,stride,slot) | dense_sym_apply P(.,inv,base,B,X) I(.,ldb,ldx,m)
+      gram P(.,S,T,G) I(.,lds,p,ldt,q) | block_mul P(.,S,C,Y) I(.,lds,p,q,ldy,acc)
+      block_residual P(.,AX,BX,lam,R,nrm) I(.,lda,ldb,m,ldr) | block_colnorm P(.,X,nrm) I(.,ldx,m)
+      block_residual_norms P(.,AX,BX,lam,R,mask,nrm3) I(.,lda,ldb,m,ldr) | block_colscale P(.,X,cs) I(.,ldx,m)
+      block_init P(.,X,sub_gid) I(.,ldx,m,seed_lo,seed_hi) | block_extract P(.,X,d,sel,ksub,zbase,Z) I(.,ldx,m)
+      z_rowmajor P(.,Z,zbase,ksub,ZR) I(.,kp) | zt_apply P(.,Z,zbase,ksub,zoff,xL,yE) I(.,kmax,dimE_total)
+      z_apply P(.,Z,zbase,ksub,zoff,yE,wL) I(.,acc)"""
+    ia = (C.c_int * max(1, len(I)))(*[int(v) for v in I])
+    da = (C.c_double * max(1, len(D)))(*[float(v) for v in D])
+    pa = (C.c_void_p * max(1, len(P)))(*[_ptr(p) for p in P])
+    rc = lib.GeneoTestPrimitive(name.encode(), ia, da, pa)
+    if expect_error:
+        return rc, lib.PCGenEOGetError(None).decode()
+    assert rc >= 0, "%s: rc %d (%s)" % (name, rc, lib.PCGenEOGetError(None).decode())
+    return rc
+
+
+def rnd(rng, *shape):
+    return (rng.random(shape) + 0.5) * rng.choice([-1.0, 1.0], size=shape)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
+
+
+def close(got, ref, bound, what):
+    err = np.abs(np.asarray(got).astype(LD) - np.asarray(ref, dtype=LD))
+    bad = ~(err <= np.asarray(bound, dtype=LD))           # (NaN counts as bad)
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(np.isnan(err), np.inf, err - bound)), err.shape)
+        raise AssertionError("%s: %d entries beyond the bound, worst at %s: err %.3e bound %.3e"
+                             % (what, int(bad.sum()), i, float(err[i]), float(np.broadcast_to(bound, err.shape)[i])))
+
+
+def blk(data, ld):
+    """(n, ld) array: data in the first columns, the sentinel in the padding columns"""
+    data = np.asarray(data, dtype=np.float64)
+    out = np.full((data.shape[0], ld), SENTF)
+    out[:, :data.shape[1]] = data
+    return out
+
+
+def pad_ok(arr, w, what):
+    assert (bits(arr[:, w:]) == SENT).all(), "%s: padding columns written" % what
+
+
+class Layout:
+    def __init__(self, sizes, off0=0):
+        self.sizes = [int(s) for s in sizes]
+        self.nsub, self.off0 = len(sizes), off0
+        self.suboff = np.concatenate([[off0], off0 + np.cumsum(self.sizes)]).astype(np.int32)
+        self.n = int(self.suboff[-1])
+
+    def rows(self, s):
+        return slice(int(self.suboff[s]), int(self.suboff[s + 1]))
+
+    def sub_of_row(self):
+        out = np.full(self.n, -1)
+        for s in range(self.nsub):
+            out[self.rows(s)] = s
+        return out
+
+
+# 1, 255, 256, 257, 1023, 1024, 1025, 3333, an empty subdomain between two others, first row != 0
+STD = Layout([1, 255, 256, 257, 1023, 1024, 0, 1025, 3333], off0=5)
+SMALL = Layout([1, 257, 0, 1025, 3333], off0=3)
+# chunk lists of 1, 255, 256, 257, 300 chunks (the strided loops of the cooperative forms wrap at 256)
+LISTS = Layout([CHUNK - 3, 255 * CHUNK - 7, 256 * CHUNK, 256 * CHUNK + 1, 300 * CHUNK - 500], off0=0)
+# the cooperative forms at the default threshold of 1024 chunks: 1025 chunks and a small subdomain
+BIG = Layout([1024 * 1024 + 77, 500], off0=0)
+
+
+class par_reduce_min:
+    """threshold of the cooperative per-subdomain reductions, restored on exit"""
+
+    def __init__(self, lib, value):
+        self.lib, self.value = lib, value
+
+    def __enter__(self):
+        self.old = self.lib.GeneoSetParReduceMin(self.value)
+
+    def __exit__(self, *a):
+        self.lib.GeneoSetParReduceMin(self.old)
+
+
+def head_ok(arr, lay, what):
+    assert (bits(arr[:lay.off0]) == SENT).all(), "%s: rows in front of the first subdomain written" % what
+
+
+def vec(lay, rng, out=False):
+    """vector over rows 0 .. n of a layout; the rows in front of the first subdomain carry the sentinel"""
+    v = np.full(lay.n, SENTF) if out else rnd(rng, lay.n)
+    v[:lay.off0] = SENTF
+    return v
+
+
+# ---------------------------------------------------------------------------------------------- index kernels
+def case_index(lib):
+    rng = np.random.default_rng(101)
+    n, nin = 5003, 3001
+    src = rnd(rng, nin)
+    idx = rng.integers(0, nin, size=n).astype(np.int32)
+    d = rnd(rng, n)
+    bi, bs, bd = Buf(lib, idx), Buf(lib, src), Buf(lib, d)
+    o = Buf(lib, np.full(n, SENTF))
+    _call(lib, "gather", I=[n], P=[o, bs, bi])
+    assert same_bits(o.get(), src[idx])
+    o = Buf(lib, np.full(n, SENTF))
+    _call(lib, "gather_mul", I=[n], P=[o, bs, bi, bd])
+    assert same_bits(o.get(), src[idx] * d)
+    # segments of length 0, 1, 2, .. and one of 300
+    lens = np.concatenate([[0, 1, 300, 0], rng.integers(0, 12, size=700)])
+    ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    nseg = len(lens)
+    sidx = rng.integers(0, nin, size=int(ptr[-1])).astype(np.int32)
+    bp, bx = Buf(lib, ptr), Buf(lib, sidx)
+    seg = np.repeat(np.arange(nseg), lens)
+    for w in (0, 3, 17):                     # 0: the vector form
+        ww = max(1, w)
+        inn = rnd(rng, nin, ww)
+        binn = Buf(lib, inn)
+        s_ref = np.zeros((nseg, ww), dtype=LD)
+        s_abs = np.zeros((nseg, ww), dtype=LD)
+        np.add.at(s_ref, seg, inn[sidx].astype(LD))
+        np.add.at(s_abs, seg, np.abs(inn[sidx]).astype(LD))
+        for acc in (0, 1):
+            y0 = rnd(rng, nseg, ww)
+            res = []
+            for rep in range(2):
+                o = Buf(lib, y0)
+                if w == 0:
+                    _call(lib, "segsum", I=[nseg, acc], P=[o, binn, bp, bx])
+                else:
+                    _call(lib, "segsum_rows", I=[nseg, w, acc], P=[o, binn, bp, bx])
+                res.append(o.get())
+            assert same_bits(res[0], res[1]), "segsum: not reproducible"
+            close(res[0], s_ref + acc * y0.astype(LD), (lens[:, None] + acc) * U * (s_abs + acc * np.abs(y0)),
+                  "segsum w=%d acc=%d" % (w, acc))
+        if w:
+            ridx = rng.integers(0, nin, size=777).astype(np.int32)
+            o = Buf(lib, np.full((777, w), SENTF))
+            _call(lib, "gather_rows", I=[777, w], P=[o, binn, Buf(lib, ridx)])
+            assert same_bits(o.get(), inn[ridx])
+
+
+# ---------------------------------------------------------------------------------------------- BLAS-1
+def case_blas1(lib):
+    rng = np.random.default_rng(102)
+    for n in (1, 255, 256, 257, 100003, 2500000):
+        x, y, d = rnd(rng, n), rnd(rng, n), rnd(rng, n)
+        bx, bdd = Buf(lib, x), Buf(lib, d)
+        o = Buf(lib, np.full(n, SENTF))
+        _call(lib, "set", I=[n], D=[-0.375], P=[o])
+        assert same_bits(o.get(), np.full(n, -0.375))
+        o = Buf(lib, np.full(n, SENTF))
+        _call(lib, "zero", I=[8 * n], P=[o])
+        assert (bits(o.get()) == 0).all()
+        o = Buf(lib, np.full(n, SENTF))
+        _call(lib, "copy", I=[n], P=[o, bx])
+        assert same_bits(o.get(), x)
+        o = Buf(lib, np.full(n, SENTF))
+        _call(lib, "xmy", I=[n], P=[o, bx, bdd])
+        assert same_bits(o.get(), x * d)
+        a, b = 1.7, -0.3
+        o = Buf(lib, y)
+        _call(lib, "axpy", I=[n], D=[a], P=[o, bx])
+        close(o.get(), a * x.astype(LD) + y, 2 * U * (np.abs(a * x) + np.abs(y)), "axpy")
+        o = Buf(lib, y)
+        _call(lib, "axpby", I=[n], D=[a, b], P=[o, bx])
+        close(o.get(), a * x.astype(LD) + b * y.astype(LD), 2 * U * (np.abs(a * x) + np.abs(b * y)), "axpby")
+        o = Buf(lib, np.full(n, np.nan))              # b == 0: y is not read
+        _call(lib, "axpby", I=[n], D=[a, 0.0], P=[o, bx])
+        assert same_bits(o.get(), a * x)
+        o = Buf(lib, y)
+        _call(lib, "axpy_dev", I=[n], D=[-1.0], P=[o, Buf(lib, np.array([a])), bx])
+        close(o.get(), y.astype(LD) - a * x.astype(LD), 2 * U * (np.abs(a * x) + np.abs(y)), "axpy_dev")
+        by = Buf(lib, y)
+        res = []
+        for rep in range(2):
+            o = Buf(lib, np.full(3, SENTF))
+            _call(lib, "dot", I=[n], P=[bx, by, o])
+            res.append(o.get())
+        assert same_bits(res[0], res[1]), "dot: not reproducible"
+        assert (bits(res[0][1:]) == SENT).all()
+        close(res[0][0], np.sum(x.astype(LD) * y), n * U * np.sum(np.abs(x * y).astype(LD)), "dot n=%d" % n)
+
+
+# ---------------------------------------------------------------------------------------------- seg_dot
+def run_seg_dot(lib, lay, seed):
+    rng = np.random.default_rng(seed)
+    x, y = vec(lay, rng), vec(lay, rng)
+    stride, slot = 5, 3
+    res = []
+    for rep in range(2):
+        o = Buf(lib, np.full((lay.nsub, stride), SENTF))
+        _call(lib, "seg_dot", I=[lay.nsub, stride, slot], P=[lay.suboff, Buf(lib, x), Buf(lib, y), o])
+        res.append(o.get())
+    assert same_bits(res[0], res[1]), "seg_dot: not reproducible"
+    got = res[0]
+    assert (bits(np.delete(got, slot, axis=1)) == SENT).all(), "seg_dot: wrote outside its slot"
+    for s in range(lay.nsub):
+        r = lay.rows(s)
+        t = x[r].astype(LD) * y[r]
+        close(got[s, slot], t.sum(), max(1, lay.sizes[s]) * U * np.abs(t).sum(), "seg_dot sub %d" % s)
+    return got[:, slot]
+
+
+def case_seg_dot(lib):
+    run_seg_dot(lib, STD, 103)
+
+
+# ---------------------------------------------------------------------------------------------- batched CG
+def cg_problem(lay, seed, zero_sub=None, diag_sub=None):
+    """block-diagonal tridiagonal SPD matrix over rows 0 .. n (no coupling across subdomain boundaries), diagonal in
+    [3, 4], off-diagonals in [-1, -0.5]: D^-1 A has its spectrum in [1/3, 5/3].  diag_sub: that subdomain's block is
+    diagonal (Jacobi-PCG converges in one step); zero_sub: b = 0 there."""
+    rng = np.random.default_rng(seed)
+    n = lay.n
+    diag = 3.0 + rng.random(n)
+    off = -(0.5 + 0.5 * rng.random(max(0, n - 1)))          # couples i and i + 1
+    last = lay.suboff[1:] - 1                                 # last row of each subdomain: no coupling to the next one
+    off[last[(last >= 0) & (last < n - 1)]] = 0.0
+    if lay.off0 > 0:
+        off[lay.off0 - 1] = 0.0
+    if diag_sub is not None:
+        r = lay.rows(diag_sub)
+        off[r.start:max(r.start, r.stop - 1)] = 0.0
+    b = rnd(rng, n)
+    if zero_sub is not None:
+        b[lay.rows(zero_sub)] = 0.0
+    a = sp.diags([off, diag, off], [-1, 0, 1], format="csr")
+    a.eliminate_zeros()
+    return a, diag, off, b
+
+
+def cg_reference(lay, diag, off, b, iters, tol2):
+    n = lay.n
+    dg, of, dinv = diag.astype(LD), off.astype(LD), 1 / diag.astype(LD)
+    x = np.zeros(n, dtype=LD)
+    r = b.astype(LD).copy()
+    z = dinv * r
+    p = z.copy()
+    sc = np.zeros((lay.nsub, 8), dtype=LD)
+    for s in range(lay.nsub):
+        q = lay.rows(s)
+        rz, rr = np.sum(r[q] * z[q]), np.sum(r[q] * r[q])
+        sc[s] = [rz, rz, 0, rr, 0, 0, 1.0 if rr > 0 else 0.0, rr]
+    parity = 0
+    for it in range(iters):
+        ap = dg * p
+        ap[:-1] += of * p[1:]
+        ap[1:] += of * p[:-1]
+        for s in range(lay.nsub):
+            q = lay.rows(s)
+            if lay.sizes[s] == 0:
+                continue
+            t = sc[s]
+            pap = np.sum(p[q] * ap[q])
+            alpha = t[parity] / pap if (t[6] != 0 and pap != 0) else LD(0)
+            x[q] += alpha * p[q]
+            r[q] -= alpha * ap[q]
+            z[q] = dinv[q] * r[q]
+            nrz, nrr = np.sum(r[q] * z[q]), np.sum(r[q] * r[q])
+            rz = t[parity]
+            beta = nrz / rz if (t[6] != 0 and rz != 0) else LD(0)
+            if t[6] != 0:
+                p[q] = z[q] + beta * p[q]
+            t[2], t[4], t[parity ^ 1], t[3], t[5] = pap, alpha, nrz, nrr, beta
+            if t[6] != 0 and nrr <= tol2 * t[7]:
+                t[6] = 0
+        parity ^= 1
+    return x, r, z, p, sc
+
+
+def run_cg(lib, lay, a, diag, b, iters, tol2, caller_precond):
+    n = lay.n
+    rng = np.random.default_rng(7)
+    bufs = [Buf(lib, vec(lay, rng, out=True)) for _ in range(4)]      # x, r, z, p
+    hb = b.copy()
+    hd = 1.0 / diag
+    sc = np.full((lay.nsub, 8), SENTF)
+    h = Spmv(a, lib)
+    rc = lib.GeneoTestCgSteps(h.h, lay.nsub, lay.suboff.ctypes.data_as(L.c_int_p), iters, tol2, caller_precond,
+                              _keep(bufs, Buf(lib, hb)).ptr, _keep(bufs, Buf(lib, hd)).ptr,
+                              bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, sc.ctypes.data_as(L.c_dbl_p))
+    assert rc == 0, lib.PCGenEOGetError(None).decode()
+    h.destroy()
+    out = [bb.get() for bb in bufs[:4]]
+    for v in out:
+        head_ok(v, lay, "cg")
+    return out + [sc]
+
+
+def _keep(lst, b):
+    lst.append(b)
+    return b
+
+
+def check_cg(lay, got, ref, what):
+    x, r, z, p, sc = got
+    rx, rr_, rz, rp, rsc = ref
+    body = slice(lay.off0, lay.n)
+    for name, g, e in (("x", x, rx), ("r", r, rr_), ("z", z, rz), ("p", p, rp)):
+        scale = float(np.max(np.abs(e[body]))) if lay.n > lay.off0 else 0.0
+        close(g[body], e[body], 1e-12 * (np.abs(e[body]) + scale), "%s: %s" % (what, name))
+    for s in range(lay.nsub):
+        scale = float(rsc[s, 7])
+        for k in (0, 1, 2, 3, 7):
+            close(sc[s, k], rsc[s, k], 1e-12 * (abs(rsc[s, k]) + scale), "%s: sub %d slot %d" % (what, s, k))
+        for k in (4, 5):
+            close(sc[s, k], rsc[s, k], 1e-12 * (abs(rsc[s, k]) + 1.0), "%s: sub %d slot %d" % (what, s, k))
+        assert sc[s, 6] == float(rsc[s, 6]), "%s: sub %d active flag %r, expected %r" % (what, s, sc[s, 6], rsc[s, 6])
+
+
+TOL2 = 1e-20      # far below the contraction of three steps on the coupled blocks, far above a converged block's rr / rr0
+
+
+def case_cg(lib, lay=STD, steps=(0, 1, 2, 3), forms=(0, 1)):
+    zero_sub, diag_sub = 2, 4                              # 256 rows with b = 0; 1023 rows that converge in one step
+    a, diag, off, b = cg_problem(lay, 104, zero_sub, diag_sub)
+    for form in forms:
+        runs = {}
+        for k in steps:
+            got = run_cg(lib, lay, a, diag, b, k, TOL2, form)
+            runs[k] = got
+            check_cg(lay, got, cg_reference(lay, diag, off, b, k, TOL2), "cg form %d, %d steps" % (form, k))
+            x, r, z, p, sc = got
+            q = lay.rows(zero_sub)
+            assert (sc[zero_sub, 4:7] == 0).all() and (bits(x[q]) == 0).all(), "b = 0: the subdomain must stay inactive"
+            if k >= 1:
+                assert sc[diag_sub, 6] == 0.0, "the converged subdomain keeps its flag"
+                assert sc[lay.nsub - 1, 6] == 1.0
+        if 1 in runs and 2 in runs:                        # a dropped flag freezes x and p; the others move
+            q = lay.rows(diag_sub)
+            assert same_bits(runs[1][0][q], runs[2][0][q]) and same_bits(runs[1][3][q], runs[2][3][q])
+            q = lay.rows(lay.nsub - 1)
+            assert not same_bits(runs[1][0][q], runs[2][0][q])
+        if 2 in runs:                                      # fixed order: the scalars are reproducible
+            again = run_cg(lib, lay, a, diag, b, 2, TOL2, form)
+            assert all(same_bits(u, v) for u, v in zip(runs[2], again)), "cg: not reproducible"
+
+
+# ---------------------------------------------------------------------------------------------- coarse space
+class ZSpace:
+    """Z_s column-major at zbase[s] (gaps between the subdomains), coarse offsets zoff in an order that is NOT the
+    subdomains' (a result written for the wrong subdomain lands on another one's entries), dimE_total larger than
+    what the local subdomains own"""
+
+    def __init__(self, lay, ksub, seed):
+        rng = np.random.default_rng(seed)
+        self.lay, self.ksub = lay, np.asarray(ksub, dtype=np.int32)
+        self.kmax = int(self.ksub.max())
+        zb, pos = [], 3
+        for s in range(lay.nsub):
+            zb.append(pos)
+            pos += int(self.ksub[s]) * lay.sizes[s] + 5
+        self.zbase = np.asarray(zb, dtype=np.int64)
+        self.zlen = pos
+        self.Z = rnd(rng, pos)
+        order = rng.permutation(lay.nsub)
+        zoff, e = np.zeros(lay.nsub, dtype=np.int32), 2
+        for s in order:
+            zoff[s] = e
+            e += int(self.ksub[s]) + 1
+        self.zoff, self.dimE = zoff, e + 4
+        self.owned = np.zeros(self.dimE, dtype=bool)
+        for s in range(lay.nsub):
+            self.owned[zoff[s]:zoff[s] + self.ksub[s]] = True
+
+    def block(self, s):
+        ns, k = self.lay.sizes[s], int(self.ksub[s])
+        return self.Z[self.zbase[s]:self.zbase[s] + k * ns].reshape(k, ns)
+
+    def dev(self, lib):
+        return Buf(lib, self.Z), Buf(lib, self.zbase), Buf(lib, self.ksub), Buf(lib, self.zoff)
+
+
+def run_zt_apply(lib, lay, ksub, seed):
+    zs = ZSpace(lay, ksub, seed)
+    rng = np.random.default_rng(seed + 1)
+    x = vec(lay, rng)
+    dZ, dzb, dk, dzo = zs.dev(lib)
+    res = []
+    for rep in range(2):
+        o = Buf(lib, np.full(zs.dimE, SENTF))
+        _call(lib, "zt_apply", I=[lay.nsub, zs.kmax, zs.dimE], P=[lay.suboff, dZ, dzb, dk, dzo, Buf(lib, x), o])
+        res.append(o.get())
+    assert same_bits(res[0], res[1]), "zt_apply: not reproducible"
+    y = res[0]
+    assert (bits(y[~zs.owned]) == 0).all(), "zt_apply: entries no local subdomain owns must be zero"
+    for s in range(lay.nsub):
+        t = zs.block(s).astype(LD) * x[lay.rows(s)]
+        close(y[zs.zoff[s]:zs.zoff[s] + zs.ksub[s]], t.sum(axis=1), max(1, lay.sizes[s]) * U * np.abs(t).sum(axis=1),
+              "zt_apply sub %d" % s)
+    return y
+
+
+def run_z_apply(lib, lay, ksub, seed):
+    zs = ZSpace(lay, ksub, seed)
+    rng = np.random.default_rng(seed + 2)
+    yE = rnd(rng, zs.dimE)
+    w0 = vec(lay, rng)
+    dZ, dzb, dk, dzo = zs.dev(lib)
+    for acc in (0, 1):
+        o = Buf(lib, w0)
+        _call(lib, "z_apply", I=[lay.nsub, acc], P=[lay.suboff, dZ, dzb, dk, dzo, Buf(lib, yE), o])
+        w = o.get()
+        head_ok(w, lay, "z_apply")
+        for s in range(lay.nsub):
+            k = int(zs.ksub[s])
+            t = zs.block(s).astype(LD) * yE[zs.zoff[s]:zs.zoff[s] + k, None]
+            old = w0[lay.rows(s)]
+            close(w[lay.rows(s)], t.sum(axis=0) + acc * old.astype(LD), (k + acc) * U * (np.abs(t).sum(axis=0) + acc * np.abs(old)),
+                  "z_apply acc=%d sub %d" % (acc, s))
+
+
+STD_K = [2, 0, 5, 1, 64, 3, 4, 256, 7]      # one subdomain without coarse vectors, one at the limit of 256
+
+
+def case_coarse_space(lib):
+    run_zt_apply(lib, STD, STD_K, 105)
+    run_z_apply(lib, STD, STD_K, 106)
+    small = Layout([3, 0, 5, 700], off0=2)
+    zs = ZSpace(small, [1, 2, 0, 3], 107)
+    rc, msg = _call(lib, "zt_apply", I=[small.nsub, 257, zs.dimE],
+                    P=[small.suboff] + list(zs.dev(lib)) + [Buf(lib, np.zeros(small.n)), Buf(lib, np.zeros(zs.dimE))],
+                    expect_error=True)
+    assert rc == -1 and "256" in msg, (rc, msg)       # refused on the host before any launch
+
+
+def case_block_extract_rowmajor(lib):
+    lay, m, ldx = STD, 6, 9
+    rng = np.random.default_rng(108)
+    ksub = np.array([2, 0, 5, 1, 6, 3, 4, 2, 6], dtype=np.int32)
+    zs = ZSpace(lay, ksub, 109)
+    X = blk(rnd(rng, lay.n, m), ldx)
+    d = vec(lay, rng)
+    sel = rng.integers(0, m, size=(lay.nsub, m)).astype(np.int32)
+    sel[:, 0] = -1                                     # the constant vector first, as core.cpp places it
+    dzb, dk = Buf(lib, zs.zbase), Buf(lib, ksub)
+    o = Buf(lib, np.full(zs.zlen, SENTF))
+    _call(lib, "block_extract", I=[lay.nsub, ldx, m], P=[lay.suboff, Buf(lib, X), Buf(lib, d), Buf(lib, sel), dk, dzb, o])
+    Z = o.get()
+    exp = np.full(zs.zlen, SENTF)
+    for s in range(lay.nsub):
+        ns, r = lay.sizes[s], lay.rows(s)
+        for j in range(ksub[s]):
+            col = d[r] if sel[s, j] < 0 else d[r] * X[r, sel[s, j]]
+            exp[zs.zbase[s] + j * ns:zs.zbase[s] + (j + 1) * ns] = col
+    assert same_bits(Z, exp), "block_extract"
+    kp = 8                                             # > every k_s: zero padding
+    o = Buf(lib, np.full((lay.n, kp), SENTF))
+    _call(lib, "z_rowmajor", I=[lay.nsub, kp], P=[lay.suboff, Buf(lib, zs.Z), dzb, dk, o])
+    ZR = o.get()
+    head_ok(ZR, lay, "z_rowmajor")
+    for s in range(lay.nsub):
+        e = np.zeros((lay.sizes[s], kp))
+        e[:, :ksub[s]] = zs.block(s).T
+        assert same_bits(ZR[lay.rows(s)], e), "z_rowmajor sub %d" % s
+
+
+def case_chol_solve(lib):
+    rng = np.random.default_rng(110)
+    for n in (1, 2, 15, 16, 17, 63, 64, 65, 1000, 1024, 1025):
+        q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        a = (q * np.linspace(1.0, 100.0, n)) @ q.T          # SPD, condition number 100
+        a = 0.5 * (a + a.T)
+        lo = np.linalg.cholesky(a)
+        b = rnd(rng, n)
+        dL, dLT = Buf(lib, lo), Buf(lib, np.ascontiguousarray(lo.T))
+        res = []
+        for rep in range(2):
+            o = Buf(lib, b)
+            rc = _call(lib, "chol_solve", I=[n], P=[dL, dLT, o])
+            res.append(o.get())
+            if n > 1024:
+                assert rc == 0 and same_bits(res[-1], b), "chol_solve beyond its capacity: false and y untouched"
+            else:
+                assert rc == 1
+        if n > 1024:
+            continue
+        assert same_bits(res[0], res[1]), "chol_solve: not reproducible"
+        x = res[0]
+        ll = lo.astype(LD)
+        resid = np.abs(ll @ (ll.T @ x.astype(LD)) - b)
+        bound = 2 * n * U * (np.abs(ll) @ (np.abs(ll.T) @ np.abs(x).astype(LD)))
+        assert (resid <= bound).all(), "chol_solve n=%d: backward error %.3e of the bound" % (n, float((resid / bound).max()))
+
+
+# ---------------------------------------------------------------------------------------------- tall-skinny blocks
+def case_block_elementwise(lib):
+    rng = np.random.default_rng(111)
+    n = 1000
+    for m in (1, 3, 20):
+        ldy, ldx, ldb, ldz = m + 1, m + 2, m + 3, m + 4
+        X, Y, B = rnd(rng, n, m), rnd(rng, n, m), rnd(rng, n, m)
+        AX, dd = rnd(rng, n, m), rnd(rng, n)
+        a, b, w = 1.7, -0.3, 0.6
+        dX, dB, dAX, ddd = Buf(lib, blk(X, ldx)), Buf(lib, blk(B, ldb)), Buf(lib, AX), Buf(lib, dd)
+        xl, yl, dl = X.astype(LD), Y.astype(LD), dd.astype(LD)[:, None]
+        for bb, y0 in ((b, Y), (0.0, np.full((n, m), np.nan))):       # b == 0: Y is not read
+            o = Buf(lib, blk(y0, ldy))
+            _call(lib, "block_axpby", I=[ldy, ldx, n, m], D=[a, bb], P=[o, dX])
+            g = o.get()
+            pad_ok(g, m, "block_axpby")
+            close(g[:, :m], a * xl + (bb * yl if bb else 0), 2 * U * (np.abs(a * X) + (np.abs(bb * Y) if bb else 0)), "block_axpby")
+            o = Buf(lib, blk(y0, ldy))
+            _call(lib, "block_rowscale", I=[ldy, ldx, n, m], D=[a, bb], P=[o, dX, ddd])
+            g = o.get()
+            pad_ok(g, m, "block_rowscale")
+            close(g[:, :m], a * dl * xl + (bb * yl if bb else 0),
+                  3 * U * (np.abs(a * dd[:, None] * X) + (np.abs(bb * Y) if bb else 0)), "block_rowscale")
+        for zg in (1, 0):
+            o = Buf(lib, blk(np.full((n, m), np.nan) if zg else X, ldx))
+            _call(lib, "jacobi_step", I=[ldx, ldb, n, m, zg], D=[w], P=[o, dB, dAX, ddd])
+            g = o.get()
+            pad_ok(g, m, "jacobi_step")
+            if zg:
+                close(g[:, :m], w * dl * B, 4 * U * np.abs(w * dd[:, None] * B), "jacobi_step zero guess")
+            else:
+                close(g[:, :m], xl + w * dl * (B.astype(LD) - AX),
+                      4 * U * (np.abs(X) + np.abs(w * dd[:, None] * B) + np.abs(w * dd[:, None] * AX)), "jacobi_step")
+        r0, ad, d0, z0 = rnd(rng, n, m), rnd(rng, n, m), rnd(rng, n, m), rnd(rng, n, m)
+        br, bd, bz = Buf(lib, r0), Buf(lib, d0), Buf(lib, blk(z0, ldz))
+        _call(lib, "cheb_update", I=[ldz, n, m], D=[a, b], P=[br, Buf(lib, ad), bd, bz, ddd])
+        r1, d1, z1 = br.get(), bd.get(), bz.get()
+        pad_ok(z1, m, "cheb_update")
+        assert same_bits(r1, r0 - ad), "cheb_update: r"
+        close(d1, a * dl * r1.astype(LD) + b * d0.astype(LD), 3 * U * (np.abs(a * dd[:, None] * r1) + np.abs(b * d0)), "cheb_update: d")
+        assert same_bits(z1[:, :m], z0 + d1), "cheb_update: z"
+
+
+def case_block_colscale_init(lib):
+    lay = STD
+    rng = np.random.default_rng(112)
+    for m in (1, 5, 20):
+        ldx = m + 3
+        X = rnd(rng, lay.n, m)
+        X[:lay.off0] = SENTF
+        cs = rnd(rng, lay.nsub, m)
+        o = Buf(lib, blk(X, ldx))
+        _call(lib, "block_colscale", I=[lay.nsub, ldx, m], P=[lay.suboff, o, Buf(lib, cs)])
+        g = o.get()
+        pad_ok(g, m, "block_colscale")
+        head_ok(g, lay, "block_colscale")
+        sub = lay.sub_of_row()[lay.off0:]
+        assert same_bits(g[lay.off0:, :m], X[lay.off0:] * cs[sub]), "block_colscale m=%d" % m
+        # block_init: splitmix64 of (seed, global subdomain id, row counted from the subdomain's first row, column)
+        gid = rng.permutation(1000)[:lay.nsub].astype(np.int32) + 17
+        seed = 0x9A3F00C512345678
+        o = Buf(lib, np.full((lay.n, ldx), SENTF))
+        _call(lib, "block_init", I=[lay.nsub, ldx, m, _i32(seed), _i32(seed >> 32)],
+              P=[lay.suboff, o, Buf(lib, gid)])
+        g = o.get()
+        pad_ok(g, m, "block_init")
+        head_ok(g, lay, "block_init")
+        row = (np.arange(lay.off0, lay.n) - lay.suboff[sub]).astype(np.uint64)
+        exp = hash_unit(np.uint64(seed), gid[sub].astype(np.uint64)[:, None], row[:, None], np.arange(m, dtype=np.uint64)[None, :])
+        exp[:, 0] = 1.0
+        assert same_bits(g[lay.off0:, :m], exp), "block_init m=%d: not the splitmix formula of backend.h, bit for bit" % m
+
+
+def _i32(v):
+    v &= 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+def hash_unit(seed, gid, row, colj):
+    """bk::hash_unit_host restated on uint64 arrays"""
+    with np.errstate(over="ignore"):
+        one = np.uint64(1)
+        z = seed + np.uint64(0x9E3779B97F4A7C15) * (gid + one) + np.uint64(0xBF58476D1CE4E5B9) * (row + one) + \
+            np.uint64(0x94D049BB133111EB) * (colj + one)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0) - 0.5
+
+
+def _sq_bound(n, v, e):
+    """sum of v^2 over n rows, v known up to e: n roundings of the sum and the product, plus the propagated error"""
+    return (2 * np.abs(v) * e + e * e).sum(axis=0) + (n + 2) * U * (v * v).sum(axis=0)
+
+
+def run_block_colnorm(lib, lay, m, seed):
+    rng = np.random.default_rng(seed)
+    ldx = m + 1
+    X = rnd(rng, lay.n, m)
+    o = Buf(lib, np.full((lay.nsub, m), SENTF))
+    _call(lib, "block_colnorm", I=[lay.nsub, ldx, m], P=[lay.suboff, Buf(lib, blk(X, ldx)), o])
+    g = o.get()
+    for s in range(lay.nsub):
+        v = X[lay.rows(s)].astype(LD)
+        close(g[s], (v * v).sum(axis=0), max(1, lay.sizes[s]) * U * (v * v).sum(axis=0), "block_colnorm m=%d sub %d" % (m, s))
+
+
+def case_block_residual(lib):
+    lay = SMALL
+    rng = np.random.default_rng(113)
+    for m in (1, 3, 20, 256):                 # 256: w = 256, K = 4 in the column-sum reduction; 20: idle threads
+        lda, ldb, ldr = m + 1, m + 2, m + 3
+        AX, BX, lam = rnd(rng, lay.n, m), rnd(rng, lay.n, m), rnd(rng, lay.nsub, m)
+        R0 = np.full((lay.n, ldr), SENTF)
+        oR, oN = Buf(lib, R0), Buf(lib, np.full((lay.nsub, m), SENTF))
+        _call(lib, "block_residual", I=[lay.nsub, lda, ldb, m, ldr],
+              P=[lay.suboff, Buf(lib, blk(AX, lda)), Buf(lib, blk(BX, ldb)), Buf(lib, lam), oR, oN])
+        R, nrm = oR.get(), oN.get()
+        pad_ok(R, m, "block_residual")
+        head_ok(R, lay, "block_residual")
+        for s in range(lay.nsub):
+            r = lay.rows(s)
+            lb = lam[s].astype(LD) * BX[r]
+            v = AX[r].astype(LD) - lb
+            e = 2 * U * (np.abs(AX[r]) + np.abs(lb))
+            close(R[r, :m], v, e, "block_residual m=%d sub %d" % (m, s))
+            close(nrm[s], (v * v).sum(axis=0), _sq_bound(lay.sizes[s], v, e), "block_residual norms m=%d sub %d" % (m, s))
+        run_block_colnorm(lib, lay, m, 114 + m)
+
+
+def case_block_residual_norms(lib):
+    lay = SMALL
+    rng = np.random.default_rng(115)
+    for m in (1, 3, 16, 20, 32, 85):
+        lda, ldb, ldr = m + 1, m + 2, m + 3
+        AX, BX, lam = rnd(rng, lay.n, m), rnd(rng, lay.n, m), rnd(rng, lay.nsub, m)
+        mask = (rng.random((lay.nsub, m)) < 0.6).astype(np.float64)
+        dA, dB, dl = Buf(lib, blk(AX, lda)), Buf(lib, blk(BX, ldb)), Buf(lib, lam)
+        for use_mask, use_nrm in ((1, 1), (0, 1), (1, 0)):
+            oR = Buf(lib, np.full((lay.n, ldr), SENTF))
+            oN = Buf(lib, np.full((lay.nsub, 3 * m), SENTF))
+            _call(lib, "block_residual_norms", I=[lay.nsub, lda, ldb, m, ldr],
+                  P=[lay.suboff, dA, dB, dl, oR, Buf(lib, mask) if use_mask else None, oN if use_nrm else None])
+            R, n3 = oR.get(), oN.get()
+            pad_ok(R, m, "block_residual_norms")
+            head_ok(R, lay, "block_residual_norms")
+            if not use_nrm:
+                assert (bits(n3) == SENT).all()
+            for s in range(lay.nsub):
+                r, ns = lay.rows(s), lay.sizes[s]
+                a, b = AX[r].astype(LD), BX[r].astype(LD)
+                lb = lam[s].astype(LD) * b
+                v = a - lb
+                e = 2 * U * (np.abs(a) + np.abs(lb))
+                mk = mask[s] if use_mask else np.ones(m)
+                close(R[r, :m], mk * v, e, "block_residual_norms R m=%d sub %d" % (m, s))
+                if use_nrm:
+                    what = "block_residual_norms m=%d sub %d" % (m, s)
+                    close(n3[s, :m], (v * v).sum(axis=0), _sq_bound(ns, v, e), what + " |r|^2")
+                    close(n3[s, m:2 * m], (a * a).sum(axis=0), max(1, ns) * U * (a * a).sum(axis=0), what + " |Ax|^2")
+                    close(n3[s, 2 * m:], (b * b).sum(axis=0), max(1, ns) * U * (b * b).sum(axis=0), what + " |Bx|^2")
+    m = 86                                     # beyond the kernel's 3 m <= 256 reducers: refused before any launch
+    z = Buf(lib, np.zeros((lay.n, m)))
+    rc, msg = _call(lib, "block_residual_norms", I=[lay.nsub, m, m, m, m],
+                    P=[lay.suboff, z, z, Buf(lib, np.zeros((lay.nsub, m))), Buf(lib, np.zeros((lay.n, m))), None,
+                       Buf(lib, np.zeros((lay.nsub, 3 * m)))], expect_error=True)
+    assert rc == -1 and "85" in msg, (rc, msg)
+
+
+def run_gram(lib, lay, p, q, seed, lds=None, ldt=None):
+    rng = np.random.default_rng(seed)
+    lds, ldt = lds or p + 2, ldt or q + 4
+    S, T = rnd(rng, lay.n, p), rnd(rng, lay.n, q)
+    dS, dT = Buf(lib, blk(S, lds)), Buf(lib, blk(T, ldt))
+    res = []
+    for rep in range(2):
+        o = Buf(lib, np.full((lay.nsub, p, q), SENTF))
+        _call(lib, "gram", I=[lay.nsub, lds, p, ldt, q], P=[lay.suboff, dS, dT, o])
+        res.append(o.get())
+    assert same_bits(res[0], res[1]), "gram: not reproducible"
+    for s in range(lay.nsub):
+        r = lay.rows(s)
+        ref = S[r].astype(LD).T @ T[r].astype(LD)
+        ab = np.abs(S[r]).astype(LD).T @ np.abs(T[r]).astype(LD)
+        close(res[0][s], ref, max(1, lay.sizes[s]) * U * ab, "gram %dx%d sub %d" % (p, q, s))
+
+
+def case_gram_block_mul_strided(lib):
+    lay = STD
+    for p, q, lds, ldt in ((3, 2, 4, 7), (16, 16, 18, 20), (32, 16, 36, 22), (20, 5, 23, 6)):
+        run_gram(lib, lay, p, q, 116 + p, lds, ldt)
+    rng = np.random.default_rng(117)
+    for p, q in ((3, 2), (16, 16), (32, 32), (20, 5), (16, 64)):
+        lds, ldy = p + 2, q + 6
+        S, Cm, Y0 = rnd(rng, lay.n, p), rnd(rng, lay.nsub, p, q), rnd(rng, lay.n, q)
+        Y0[:lay.off0] = SENTF
+        dS, dC = Buf(lib, blk(S, lds)), Buf(lib, Cm)
+        for acc in (0, 1):
+            o = Buf(lib, blk(Y0, ldy))
+            _call(lib, "block_mul", I=[lay.nsub, lds, p, q, ldy, acc], P=[lay.suboff, dS, dC, o])
+            Y = o.get()
+            pad_ok(Y, q, "block_mul")
+            head_ok(Y, lay, "block_mul")
+            for s in range(lay.nsub):
+                r = lay.rows(s)
+                ref = S[r].astype(LD) @ Cm[s].astype(LD) + acc * Y0[r].astype(LD)
+                ab = np.abs(S[r]).astype(LD) @ np.abs(Cm[s]).astype(LD) + acc * np.abs(Y0[r])
+                close(Y[r, :q], ref, (p + acc) * U * ab, "block_mul %dx%d acc=%d sub %d" % (p, q, acc, s))
+
+
+def case_dense_sym_apply(lib):
+    lay = Layout([1, 7, 0, 8, 9, 257, 1025], off0=3)
+    rng = np.random.default_rng(118)
+    m, ldb, ldx = 3, 4, 5
+    base, pos, mats = [], 2, []
+    for ns in lay.sizes:
+        base.append(pos)
+        a = rnd(rng, ns, ns)
+        mats.append(a + a.T)
+        pos += ns * ns + 3
+    inv = rnd(rng, pos)
+    for s, a in enumerate(mats):
+        inv[base[s]:base[s] + a.size] = a.reshape(-1)
+    B = rnd(rng, lay.n, m)
+    o = Buf(lib, np.full((lay.n, ldx), SENTF))
+    _call(lib, "dense_sym_apply", I=[lay.nsub, ldb, ldx, m],
+          P=[lay.suboff, Buf(lib, inv), Buf(lib, np.asarray(base, dtype=np.int64)), Buf(lib, blk(B, ldb)), o])
+    X = o.get()
+    pad_ok(X, m, "dense_sym_apply")
+    head_ok(X, lay, "dense_sym_apply")
+    for s, a in enumerate(mats):
+        r = lay.rows(s)
+        close(X[r, :m], a.astype(LD) @ B[r].astype(LD), max(1, lay.sizes[s]) * U * (np.abs(a).astype(LD) @ np.abs(B[r]).astype(LD)),
+              "dense_sym_apply sub %d" % s)
+
+
+# ---------------------------------------------------------------------------------------------- cooperative forms
+LISTS_K = [3, 0, 2, 1, 2]
+
+
+def case_chunk_lists_cooperative(lib):
+    """chunk lists of 1, 255, 256, 257, 300 chunks with the threshold at 0 (k_sub_totals, k_seg_dot2_big,
+    k_zt_reduce_big, k_gram_reduce_z / _fin) and at its default (the ordinary forms), each against numpy"""
+    lay = LISTS
+    for thr in (0, 1024):
+        with par_reduce_min(lib, thr):
+            a = run_seg_dot(lib, lay, 119)
+            y = run_zt_apply(lib, lay, LISTS_K, 120)
+            run_gram(lib, lay, 3, 2, 121)
+            if thr == 0:                       # (the MFMA partials through the cooperative reduction; the ordinary
+                run_gram(lib, lay, 16, 16, 122)    #  form of this shape runs in case_gram_block_mul_strided)
+            case_cg(lib, Layout(lay.sizes[:1] + [0] + lay.sizes[1:3] + [1023] + lay.sizes[3:]), steps=(3,), forms=(0, 1))
+        if thr == 0:
+            a0, y0 = a, y
+    # the two forms differ in summation order only
+    assert np.allclose(a, a0, rtol=1e-9, atol=0) and np.allclose(y, y0, rtol=1e-9, atol=1e-9)
+
+
+def case_default_threshold_cooperative(lib):
+    """1024 x 1024 + 77 rows are 1025 chunks: above the DEFAULT threshold, the cooperative forms for real"""
+    lay = BIG
+    with par_reduce_min(lib, 1024):
+        run_seg_dot(lib, lay, 123)
+        run_zt_apply(lib, lay, [3, 0], 124)
+        run_z_apply(lib, lay, [3, 0], 125)
+        run_block_colnorm(lib, lay, 4, 126)
+        a, diag, off, b = cg_problem(lay, 127)
+        for form in (0, 1):
+            got = run_cg(lib, lay, a, diag, b, 2, TOL2, form)
+            check_cg(lay, got, cg_reference(lay, diag, off, b, 2, TOL2), "cg (default threshold) form %d" % form)
+
+
+# ---------------------------------------------------------------------------------------------- set-up on CSR
+def band(n, seed, ncols=None, per_row=6, hw=12):
+    """diagonally dominant band matrix with a full diagonal (entries of magnitude [0.5, 1.5) off it)"""
+    rng = np.random.default_rng(seed)
+    ncols = ncols or n
+    rows = np.repeat(np.arange(n), per_row)
+    cols = np.clip(rows * ncols // n + rng.integers(-hw, hw + 1, size=len(rows)), 0, ncols - 1)
+    a = sp.csr_matrix((rnd(rng, len(rows)), (rows, cols)), shape=(n, ncols))
+    if ncols == n:
+        a = a + sp.diags(10.0 + rng.random(n))
+    a = a.tocsr()
+    a.sum_duplicates()
+    a.sort_indices()
+    return a
+
+
+def csr_op(lib, op, a, b=None, I=(), D=(), P=(), nrows=None, ncols=None):
+    """GeneoTestCsrOp; returns (nnz or error code, csr_matrix or None)"""
+    aa = _csr_arrays(a)
+    sa = _csr_struct(aa)
+    sb = None
+    if b is not None:
+        ba = _csr_arrays(b)
+        sb = _csr_struct(ba)
+    ia = (C.c_int * max(1, len(I)))(*[int(v) for v in I])
+    da = (C.c_double * max(1, len(D)))(*[float(v) for v in D])
+    pa = (C.c_void_p * max(1, len(P)))(*[_ptr(p) for p in P])
+    pb = C.byref(sb) if sb is not None else None
+    nnz = lib.GeneoTestCsrOp(op, C.byref(sa), pb, ia, da, pa, None, None, None, 0)
+    assert nnz != -2, lib.PCGenEOGetError(None).decode()
+    if nnz < 0 or op == 4:
+        return nnz, None
+    nrows = nrows if nrows is not None else len(aa[0]) - 1
+    rp, col, val = np.zeros(nrows + 1, dtype=np.int32), np.zeros(max(1, nnz), dtype=np.int32), np.full(max(1, nnz), SENTF)
+    nnz2 = lib.GeneoTestCsrOp(op, C.byref(sa), pb, ia, da, pa, rp.ctypes.data_as(L.c_int_p), col.ctypes.data_as(L.c_int_p),
+                              val.ctypes.data_as(L.c_dbl_p), nnz)
+    assert nnz2 == nnz
+    return nnz, (rp, col[:nnz], val[:nnz])
+
+
+def case_csr_diag_recip(lib):
+    """csr_diag sums the entries (r, r) of a row: 0 without one, the sum with an explicit duplicate (both uploaders keep
+    the CSR arrays as given, duplicates included)"""
+    rng = np.random.default_rng(128)
+    n = 1500
+    rp, col, val = [0], [], []
+    for i in range(n):
+        c = sorted(set(rng.integers(0, n, size=4).tolist()) - {i})
+        kind = i % 3                                     # 0: no diagonal entry, 1: one, 2: an explicit duplicate
+        c = sorted(c + [i] * kind)
+        col += c
+        val += rnd(rng, len(c)).tolist()
+        rp.append(len(col))
+    rp, col, val = np.asarray(rp, dtype=np.int32), np.asarray(col, dtype=np.int32), np.asarray(val)
+    o = Buf(lib, np.full(n, SENTF))
+    nnz, _ = csr_op(lib, 4, (rp, col, val), P=[o])
+    assert nnz == len(col)
+    dg = o.get()
+    for i in range(n):
+        v = val[rp[i]:rp[i + 1]][col[rp[i]:rp[i + 1]] == i]
+        exp = 0.0 if len(v) == 0 else (v[0] if len(v) == 1 else v[0] + v[1])
+        assert dg[i] == exp and (len(v) or bits(np.array([dg[i]]))[0] == 0), "csr_diag row %d" % i
+    # recip_positive: zeros, negatives, NaN are counted and left bit-unchanged
+    for n in (1, 257, 70001):
+        x = rng.random(n) + 0.5
+        bad = rng.random(n) < 0.1
+        x[bad] = rng.choice([0.0, -0.0, -2.5, np.nan, -np.inf], size=int(bad.sum()))
+        o = Buf(lib, x)
+        cnt = _call(lib, "recip_positive", I=[n], P=[o])
+        g = o.get()
+        assert cnt == int(bad.sum())
+        assert same_bits(g[bad], x[bad]) and same_bits(g[~bad], 1.0 / x[~bad]), "recip_positive"
+
+
+def case_csr_remap_scaled_alias(lib):
+    rng = np.random.default_rng(129)
+    n = 3000
+    a = band(n, 130)
+    arp, acol, aval = _csr_arrays(a)
+    cmap = rng.permutation(2 * n)[:n].astype(np.int32)
+    nnz, (rp, col, val) = csr_op(lib, 0, a, P=[Buf(lib, cmap)])
+    assert nnz == a.nnz and (rp == arp).all() and (col == cmap[acol]).all() and same_bits(val, aval), "csr_remap_columns"
+    rs, cs = rnd(rng, n), rnd(rng, n)
+    rowi = np.repeat(np.arange(n), np.diff(arp))
+    for use_r, use_c in ((1, 0), (0, 1), (1, 1)):
+        nnz, (rp, col, val) = csr_op(lib, 1, a, I=[0, 0, 0, 0, 0], D=[0.0],
+                                     P=[Buf(lib, rs) if use_r else None, Buf(lib, cs) if use_c else None])
+        exp = (rs[rowi] if use_r else 1.0) * aval * (cs[acol] if use_c else 1.0)
+        assert (rp == arp).all() and (col == acol).all() and same_bits(val, exp), "csr_scaled_alias %d%d" % (use_r, use_c)
+    # A diag(dinv) marked col_is_dinv under the EPI_PRE epilogue == the unscaled matrix under the same epilogue
+    dinv, w = 1.0 / a.diagonal(), 0.7
+    absa = abs(a)
+    for m, ldy, ldb, ldz in ((1, 1, 1, 1), (1, 2, 3, 4), (3, 4, 5, 6)):    # contiguous vectors take the SpMV kernels
+        B = rnd(rng, n, m)
+        oY, oZ = Buf(lib, np.full((n, ldy), SENTF)), Buf(lib, np.full((n, ldz), SENTF))
+        dB = Buf(lib, blk(B, ldb))
+        csr_op(lib, 1, a, I=[1, m, ldy, ldb, ldz], D=[w], P=[None, Buf(lib, dinv), oY, dB, oZ, Buf(lib, dinv)])
+        Y, Z = oY.get(), oZ.get()
+        pad_ok(Y, m, "EPI_PRE Y")
+        pad_ok(Z, m, "EPI_PRE Z")
+        zl = w * dinv.astype(LD)[:, None] * B
+        t = np.abs(np.asarray(zl, dtype=np.float64))
+        yref = B.astype(LD) - _ld_matmul(a, zl)
+        ybound = (a.getnnz(axis=1).max() + 4) * U * (np.abs(B) + absa @ t)
+        close(Z[:, :m], zl, 2 * U * np.abs(zl), "EPI_PRE Z (scaled alias)")
+        close(Y[:, :m], yref, ybound, "EPI_PRE Y (scaled alias) m=%d" % m)
+        h = Spmv(a, lib)
+        y2 = h.fused(EPI_PRE, B=B, dinv=dinv, w=w)
+        h.destroy()
+        y2 = y2[0]
+        close(np.asarray(y2).reshape(n, m), yref, ybound, "EPI_PRE Y (unscaled) m=%d" % m)
+
+
+def _ld_matmul(a, x):
+    """csr (float64) times a dense longdouble block, accumulated in longdouble"""
+    a = a.tocsr()
+    out = np.zeros((a.shape[0], x.shape[1]), dtype=LD)
+    rowi = np.repeat(np.arange(a.shape[0]), np.diff(a.indptr))
+    np.add.at(out, rowi, a.data.astype(LD)[:, None] * x[a.indices])
+    return out
+
+
+def case_prolongators_post_matrix(lib):
+    rng = np.random.default_rng(131)
+    n = 2000
+    a = band(n, 132)
+    agg = (rng.permutation(n) // 3).astype(np.int32)
+    nagg = int(agg.max()) + 1
+    dinv, w = 1.0 / a.diagonal(), 0.55
+    dagg, dd = Buf(lib, agg), Buf(lib, dinv)
+    nnz, (rp, col, val) = csr_op(lib, 2, a, I=[nagg, 0], D=[w], P=[dagg, dd])
+    assert nnz == n and (rp == np.arange(n + 1)).all() and (col == agg).all() and (val == 1.0).all(), "csr_tentative_prolongator"
+    p0 = sp.csr_matrix((np.ones(n), agg, np.arange(n + 1)), shape=(n, nagg))
+    res = [csr_op(lib, 2, a, I=[nagg, 1], D=[w], P=[dagg, dd])[1] for rep in range(2)]
+    assert all((u == v).all() for u, v in zip(res[0][:2], res[1][:2])) and same_bits(res[0][2], res[1][2]), \
+        "smooth_prolongator: not reproducible"
+    rp, col, val = res[0]
+    pat = (abs(a) @ p0).tocsr()
+    pat.sort_indices()
+    assert (rp == pat.indptr).all() and (col == pat.indices).all(), "pattern of A P0"
+    rowi = np.repeat(np.arange(n), np.diff(rp))
+    ap0 = _ld_matmul(a, p0.toarray().astype(LD))
+    ab0 = np.asarray((abs(a) @ p0).todense())
+    own = (col == agg[rowi]).astype(np.float64)
+    close(val, own - w * dinv[rowi].astype(LD) * ap0[rowi, col],
+          (a.getnnz(axis=1).max() + 3) * U * (own + np.abs(w * dinv[rowi]) * ab0[rowi, col]), "smooth_prolongator")
+    # post_matrix: M = P - w diag(dinv) AP on the pattern of AP
+    p = sp.csr_matrix((val, col, rp), shape=(n, nagg))
+    ap = (a @ p).tocsr()
+    ap.sort_indices()
+    nnz, (rp2, col2, val2) = csr_op(lib, 3, ap, p, D=[w], P=[dd])
+    assert nnz == ap.nnz and (rp2 == ap.indptr).all() and (col2 == ap.indices).all()
+    rowi = np.repeat(np.arange(n), np.diff(ap.indptr))
+    pd = np.asarray(p.todense())
+    pv = pd[rowi, ap.indices]
+    close(val2, pv - w * dinv[rowi].astype(LD) * ap.data, 3 * U * (np.abs(pv) + np.abs(w * dinv[rowi] * ap.data)), "post_matrix")
+    # one entry of P without a slot in AP
+    pl = p.tolil()
+    free = np.setdiff1d(np.arange(nagg), ap.indices[ap.indptr[7]:ap.indptr[8]])
+    pl[7, free[0]] = 0.25
+    nnz, _ = csr_op(lib, 3, ap, pl.tocsr(), D=[w], P=[dd])
+    assert nnz == -3, "post_matrix must return false when an entry of P has no slot in AP"
+
+
+def case_csr_finish_spmv(lib):
+    rng = np.random.default_rng(133)
+    n, k, m = 1500, 900, 1100
+    a, b = band(n, 134, ncols=k), band(k, 135, ncols=m)
+    x = rnd(rng, m)
+    res = []
+    for rep in range(2):
+        o = Buf(lib, np.full(n, SENTF))
+        nnz, (rp, col, val) = csr_op(lib, 5, a, b, I=[m], P=[Buf(lib, x), o])
+        res.append((o.get(), val))
+    assert same_bits(res[0][0], res[1][0]) and same_bits(res[0][1], res[1][1]), "product + SpMV: not reproducible"
+    pat = (abs(a) @ abs(b)).tocsr()
+    pat.sort_indices()
+    assert (rp == pat.indptr).all() and (col == pat.indices).all()
+    xl = x.astype(LD)[:, None]
+    ref = _ld_matmul(a, _ld_matmul(b, xl))[:, 0]
+    ab = (abs(a) @ (abs(b) @ np.abs(x)))
+    terms = a.getnnz(axis=1).max() * b.getnnz(axis=1).max() + 2
+    close(res[0][0], ref, terms * U * ab, "csr_finish + spmv")
+
+
+CASES = [case_index, case_blas1, case_seg_dot, case_cg, case_coarse_space, case_block_extract_rowmajor, case_chol_solve,
+         case_block_elementwise, case_block_colscale_init, case_block_residual, case_block_residual_norms,
+         case_gram_block_mul_strided, case_dense_sym_apply, case_chunk_lists_cooperative, case_default_threshold_cooperative,
+         case_csr_diag_recip, case_csr_remap_scaled_alias, case_prolongators_post_matrix, case_csr_finish_spmv]
+
+# ---------------------------------------------------------------------------------------------- inventory
+# every function declared in namespace bk (csrc/backend.h) -> the cases that call it alone (functions of this module,
+# or tests of test_gpu_kernels.py by name), or ("exempt", reason) for functions without numeric output of a kernel.
+_K = "test_gpu_kernels.py::"
+INVENTORY = {
+    # exempt: allocation and copies
+    **{f: ("exempt", "allocation") for f in ("alloc", "dfree", "alloc_cache_release", "mem_info", "alloc_stats",
+                                             "pinned_alloc", "pinned_free")},
+    **{f: ("exempt", "copy") for f in ("h2d", "d2h", "d2d", "h2d_async", "d2h_after", "csr_upload_raw", "csr_download")},
+    # exempt: streams, devices, events, graphs
+    **{f: ("exempt", "stream") for f in ("set_stream", "get_stream", "sync", "side_stream_begin", "side_stream_end")},
+    **{f: ("exempt", "device") for f in ("device_count", "set_device", "current_device", "thread_device_check")},
+    **{f: ("exempt", "event") for f in ("event_create", "event_record", "event_elapsed_ms", "event_destroy")},
+    **{f: ("exempt", "graph") for f in ("graph_capture_begin", "graph_capture_end", "graph_launch", "graph_destroy")},
+    **{f: ("exempt", "profiling") for f in ("spmv_profile_start", "spmv_profile_stop", "kernel_profile_start",
+                                            "kernel_profile_stop", "kernel_profile_get")},
+    **{f: ("exempt", "switch") for f in ("set_spmv_kind", "set_mfma", "set_variant", "set_par_reduce_min",
+                                         "get_par_reduce_min")},
+    **{f: ("exempt", "predicate") for f in ("csr_has_lp", "csr_fusable", "spmm_dual_available", "lobpcg_update32_available",
+                                            "spmv_profiling")},
+    **{f: ("exempt", "destructor") for f in ("csr_free", "csr_free_lp", "chunks_free")},
+    "name": ("exempt", "name"), "spmv_kernel_name": ("exempt", "name"), "hash_unit_host": ("exempt", "host"),
+    # tested in test_gpu_kernels.py
+    "csr_upload": [_K + "test_spmv", "case_csr_remap_scaled_alias"],
+    "spmv": [_K + "test_spmv", "case_cg"],
+    "spmm_strided": [_K + "test_spmm"],
+    "spmm_fused": [_K + "test_fused_multigrid_epilogues", "case_csr_remap_scaled_alias"],
+    "csr_make_lp": [_K + "test_single_precision_companion"],
+    "spmv_lp": [_K + "test_single_precision_companion"],
+    "spmv_fused_lp": [_K + "test_single_precision_companion"],
+    "spgemm": [_K + "test_device_sparse_products", "case_csr_finish_spmv"],
+    "transpose": [_K + "test_device_sparse_products"],
+    "sell_values_on": [_K + "test_spmm_dual_two_operators_one_pass"],
+    "spmm_dual": [_K + "test_spmm_dual_two_operators_one_pass"],
+    "spmm_dual_residual": [_K + "test_lean_lobpcg_update_and_residual"],
+    "gram2": [_K + "test_gram_two_left_blocks"],
+    "lobpcg_update32": [_K + "test_fused_lobpcg_update"],
+    "lobpcg_update32_basis": [_K + "test_lean_lobpcg_update_and_residual"],
+    "selftest_mfma_f64": [_K + "test_mfma_lane_map"],
+    # this module
+    "gather": ["case_index"], "gather_mul": ["case_index"], "segsum": ["case_index"], "gather_rows": ["case_index"],
+    "segsum_rows": ["case_index"],
+    "set": ["case_blas1"], "zero": ["case_blas1", "case_coarse_space"], "copy": ["case_blas1"], "axpy": ["case_blas1"],
+    "axpby": ["case_blas1"], "xmy": ["case_blas1"], "axpy_dev": ["case_blas1"], "dot": ["case_blas1"],
+    "chunks_upload": ["case_seg_dot", "case_chunk_lists_cooperative"],
+    "seg_dot": ["case_seg_dot", "case_chunk_lists_cooperative", "case_default_threshold_cooperative"],
+    "cg_start": ["case_cg", "case_chunk_lists_cooperative", "case_default_threshold_cooperative"],
+    "seg_pap": ["case_cg"], "seg_partial": ["case_cg"], "cg_set_rz": ["case_cg"],
+    "cg_update": ["case_cg", "case_default_threshold_cooperative"],
+    "cg_direction": ["case_cg", "case_default_threshold_cooperative"],
+    "dense_sym_apply": ["case_dense_sym_apply"],
+    "gram": ["case_gram_block_mul_strided", "case_chunk_lists_cooperative", _K + "test_gram"],
+    "block_mul": ["case_gram_block_mul_strided", _K + "test_block_mul"],
+    "block_residual": ["case_block_residual"],
+    "block_colnorm": ["case_block_residual", "case_default_threshold_cooperative"],
+    "block_residual_norms": ["case_block_residual_norms"],      # m = 86 is refused by both backends
+    "block_axpby": ["case_block_elementwise"], "block_rowscale": ["case_block_elementwise"],
+    "jacobi_step": ["case_block_elementwise"], "cheb_update": ["case_block_elementwise"],
+    "block_colscale": ["case_block_colscale_init"], "block_init": ["case_block_colscale_init"],
+    "block_extract": ["case_block_extract_rowmajor"], "z_rowmajor": ["case_block_extract_rowmajor"],
+    "zt_apply": ["case_coarse_space", "case_chunk_lists_cooperative", "case_default_threshold_cooperative"],  # kmax = 257 refused by both
+    "z_apply": ["case_coarse_space", "case_default_threshold_cooperative"],
+    "chol_solve": ["case_chol_solve"],
+    "csr_diag": ["case_csr_diag_recip"], "recip_positive": ["case_csr_diag_recip"],
+    "csr_tentative_prolongator": ["case_prolongators_post_matrix"],
+    "smooth_prolongator": ["case_prolongators_post_matrix"],
+    "post_matrix": ["case_prolongators_post_matrix"],
+    "csr_remap_columns": ["case_csr_remap_scaled_alias"],
+    "csr_scaled_alias": ["case_csr_remap_scaled_alias"],
+    "csr_finish": ["case_csr_finish_spmv"],
+}
+# the only reasons an exemption may carry (functions that produce no numeric output of a kernel)
+EXEMPT_REASONS = {"allocation", "copy", "stream", "device", "event", "graph", "profiling", "switch", "predicate",
+                  "destructor", "name", "host"}

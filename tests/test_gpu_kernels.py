@@ -1,5 +1,8 @@
-"""-m gpu: every hand-written HIP kernel against numpy/scipy (FP64, tolerance 1e-12 relative unless
-stated), called through the C ABI of libgeneopc.so."""
+"""-m gpu: the sparse products (SpMV / SpMM / fused epilogues / companion / SpGEMM), gram, gram2, block_mul and the fused
+LOBPCG update against numpy/scipy (FP64, tolerance 1e-12 relative unless stated), called through the C ABI of
+libgeneopc.so.  The other primitives of csrc/backend.h are tested one by one in test_gpu_primitives.py; the table
+primitive_cases.INVENTORY maps every declaration of backend.h to its cases (here or there) and
+test_hostsim_primitives.py fails when a declaration has none."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
