@@ -157,6 +157,7 @@ SYMBOLS = {
                                   c_int_p, c_dbl_p, c_dbl_p]),
     "GeneoSpmvFusedSingle": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_double]),
+    "GeneoSpmvOffsetInfo": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "GeneoSetParReduceMin": (C.c_int, [C.c_int]),
     "GeneoTestLobpcgUpdate": (C.c_int, [C.c_int, c_int_p] + [c_dbl_p] * 11),
     "GeneoBlockKernel": (C.c_int, [C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p,
@@ -168,10 +169,16 @@ SYMBOLS = {
 }
 
 
+# introspection hooks a host build of the library may lack: bound when exported
+OPTIONAL = {"GeneoSpmvOffsetInfo"}
+
+
 def bind(path):
     """dlopen `path` and attach the prototypes of include/geneo_c.h.  Raises if a symbol is missing."""
     lib = C.CDLL(path, mode=C.RTLD_LOCAL)
     for name, (res, args) in SYMBOLS.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)       # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -82,6 +82,16 @@ struct Csr {
   float* lp_val = nullptr;
   unsigned short* lp_col = nullptr;
   int* lp_base = nullptr;      // 4 x nslice: {b0, b1, ks, -} per slice (ks = INT_MAX: one base)
+  // offset-coded columns of stencil-like slices (built with lp_col, same lifetime, borrowed by aliases as lp_col is): in
+  // a coded slice (at most 8 entries per row) every column is `row + one of at most 8 constants`; off_rec holds the
+  // slice's sorted distinct offsets col - row (unused slots 0; off_rec[8 s] = INT_MIN: the slice is not coded and keeps
+  // lp_col / lp_base), off_mask one presence byte per row: bit j set = the row holds offset j, and the row's p-th stored
+  // entry is its p-th set bit.  1 + 32 / 64 = 1.5 bytes per row instead of 2 bytes per entry.  Both arrays are null
+  // unless at least 90 % of the slices are coded (off_coded / off_nnz still report what the detection found).
+  unsigned char* off_mask = nullptr;   // 64 x nslice
+  int* off_rec = nullptr;              // 8 x nslice
+  int off_coded = 0;                   // coded slices
+  int64_t off_nnz = 0;                 // stored entries (padding included) of the coded slices
   int vec_lpr = 0;             // > 0: long / ragged rows (restriction, coarse Galerkin operators): the SpMV runs the
                                // lanes-per-row CSR kernel with this many lanes per row instead of the slices
 };

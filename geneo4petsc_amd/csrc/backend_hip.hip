@@ -84,6 +84,10 @@ static bool g_init = false;
 // set_variant("lp_fixed", 0) / GENEO_LP_FIXED=0: the 4-step loop for every slice of k_spmv_sell_lp instead of its two-latency
 // forms (validation, A/B)
 __device__ int g_lp_no_fixed = 0;
+// set_variant("sell_offsets", 0) / GENEO_SELL_OFFSETS=0: matrices that carry offset-coded columns (Csr::off_mask) run the
+// kernels that read their stored columns all the same (validation, A/B).  A host-side choice between instantiations, made at
+// launch: changing it while a captured inner-PCG graph exists is not supported (the graph keeps the launches it recorded).
+static bool g_sell_offsets = !(getenv("GENEO_SELL_OFFSETS") && atoi(getenv("GENEO_SELL_OFFSETS")) == 0);
 
 static void lazy_init() {
   if (g_init) return;
@@ -865,6 +869,7 @@ __global__ void k_map_int(int* __restrict__ out, const int* __restrict__ in, con
 }
 Csr csr_remap_columns(const Csr& a, const int* map_dev) {
   Csr b = a;   // scalars (n, nnz, nslice, nlong, max_row, vec_lpr, ...) carry over; the arrays are re-made below
+  b.off_mask = nullptr; b.off_rec = nullptr; b.off_coded = 0; b.off_nnz = 0;   // coded for a's columns, not the mapped ones
   auto dup = [](const void* src, size_t bytes) -> void* {
     void* p = alloc(std::max<size_t>(bytes, 8));
     if (src && bytes) d2d(p, src, bytes);
@@ -1669,8 +1674,9 @@ bool post_matrix(Csr& ap, const Csr& p, const double* dinv, double w) {
 
 void csr_free_lp(Csr& a) {
   dfree(a.lp_val);
-  if (!a.alias) { dfree(a.lp_col); dfree(a.lp_base); }
+  if (!a.alias) { dfree(a.lp_col); dfree(a.lp_base); dfree(a.off_mask); dfree(a.off_rec); }
   a.lp_val = nullptr; a.lp_col = nullptr; a.lp_base = nullptr;
+  a.off_mask = nullptr; a.off_rec = nullptr; a.off_coded = 0; a.off_nnz = 0;
 }
 void csr_free(Csr& a) {
   csr_free_lp(a);
@@ -1707,6 +1713,7 @@ Csr csr_scaled_alias(const Csr& a, const double* row_scale, const double* col_sc
   Csr b = a;
   b.alias = true;
   b.lp_val = nullptr; b.lp_col = nullptr; b.lp_base = nullptr;
+  b.off_mask = nullptr; b.off_rec = nullptr; b.off_coded = 0; b.off_nnz = 0;
   b.col_scaled = col_is_dinv;
   b.val = (double*)alloc(sizeof(double) * std::max<size_t>(1, (size_t)a.nnz));
   b.sl_val = (double*)alloc(sizeof(double) * (size_t)std::max<int64_t>(1, a.sl_nnz));
@@ -1781,16 +1788,63 @@ __device__ __forceinline__ int4 lp_base_of(const int* __restrict__ base, int s) 
 // k_spmv_sell<4, ..> below (KW / 4 rounds into four accumulators, the remainder into the first, then acc0 + acc1 + acc2 +
 // acc3): bit-identical to it.  (k_spmv_sell_p8 further down is the round-3 form of the same idea with another summation
 // order; the single-precision companion kernels have theirs in lp_row_sum_fixed.)
-template <int KW, bool NT, typename COLT>
-__device__ __forceinline__ double spmv_row_sum_fixed(const COLT* __restrict__ col, const double* __restrict__ val, int64_t e0,
-                                                     const int4 cb, const double* __restrict__ x) {
+// Where the fixed forms (here and lp_row_sum_fixed) take the columns c[u] of a row from: `at` runs inside the load loop,
+// next to the value load of the same entry; `finish` runs between the last value load and the first gather.
+// ColsStored: the stored column stream (COLT = int: sl_col; unsigned short: lp_col, offsets from the slice's bases cb).
+template <typename COLT, bool NT>
+struct ColsStored {
+  const COLT* __restrict__ col;
+  int4 cb;
+  __device__ __forceinline__ int at(int u, int64_t e0) const {
+    return (u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e0 + 64 * u) : col[e0 + 64 * u]);
+  }
+  template <int KW>
+  __device__ __forceinline__ void finish(int (&)[KW]) const {}
+};
+// ColsOffset: an offset-coded slice (Csr::off_rec / off_mask, k_off_code): c[u] = row + off[slot(u)], slot(u) = the u-th set
+// bit of the row's presence mask; no column stream.  The slice's offsets sit in scalar registers.  All-present rows (every
+// lane's mask has exactly the KW low bits: an interior slice of a stencil) take c[u] = row + off[u] without the bit walk;
+// otherwise they are fetched by lane permute from `ov` (lane j of every eight holds off[j], loaded with the mask).  Padding positions (mask exhausted) decode
+// to `pad`, an in-range column (the row's own index, clamped to the last row in the tail of the last slice).  The stored
+// columns point their padding at the row's LAST column instead (k_sell_fill); either is multiplied by a stored 0.0, so the
+// two paths give the same bits for every finite x -- with an Inf or NaN in x the 0 * x[pad] terms can differ.
+constexpr int OFF_NONE = (int)0x80000000;   // off_rec[8 s]: slice s is not coded
+struct ColsOffset {
+  int4 o0, o1;     // wave-uniform
+  unsigned char m8;   // as loaded: widened in finish(), behind the value loads, so that they are not held back by it
+  int ov;
+  int r, pad;
+  __device__ __forceinline__ int at(int, int64_t) const { return 0; }
+  template <int KW>
+  __device__ __forceinline__ void finish(int (&c)[KW]) const {
+    constexpr unsigned full = (1u << KW) - 1u;
+    const unsigned m = m8;
+    const int off[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+    if (__ballot(m != full) == 0) {
+#pragma unroll
+      for (int u = 0; u < KW; ++u) c[u] = r + off[u];
+    } else {
+      unsigned mm = m;
+#pragma unroll
+      for (int u = 0; u < KW; ++u) {
+        const int o = __builtin_amdgcn_ds_bpermute((__ffs(mm) - 1) * 4, ov);
+        c[u] = mm ? r + o : pad;
+        mm &= mm - 1u;
+      }
+    }
+  }
+};
+template <int KW, bool NT, typename SRC>
+__device__ __forceinline__ double spmv_row_sum_fixed(const SRC& src, const double* __restrict__ val, int64_t e0,
+                                                     const double* __restrict__ x) {
   int c[KW];
   double v[KW];
 #pragma unroll
   for (int u = 0; u < KW; ++u) {
-    c[u] = (u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e0 + 64 * u) : col[e0 + 64 * u]);
+    c[u] = src.at(u, e0);
     v[u] = NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u];
   }
+  src.template finish<KW>(c);
   double xv[KW];
 #pragma unroll
   for (int u = 0; u < KW; ++u) xv[u] = x[c[u]];
@@ -1804,32 +1858,60 @@ __device__ __forceinline__ double spmv_row_sum_fixed(const COLT* __restrict__ co
   for (int k = 4 * NG; k < KW; ++k) acc[0] += v[k] * xv[k];
   return ((acc[0] + acc[1]) + acc[2]) + acc[3];
 }
-template <int UNR, bool NT, typename COLT = int>
+// the fixed form of a slice of wd = 1 .. 8 entries per row (wd is wave-uniform)
+template <bool NT, typename SRC>
+__device__ __forceinline__ double spmv_row_sum_narrow(int wd, const SRC& src, const double* __restrict__ val, int64_t e0,
+                                                      const double* __restrict__ x) {
+  switch (wd) {
+    case 1: return spmv_row_sum_fixed<1, NT>(src, val, e0, x);
+    case 2: return spmv_row_sum_fixed<2, NT>(src, val, e0, x);
+    case 3: return spmv_row_sum_fixed<3, NT>(src, val, e0, x);
+    case 4: return spmv_row_sum_fixed<4, NT>(src, val, e0, x);
+    case 5: return spmv_row_sum_fixed<5, NT>(src, val, e0, x);
+    case 6: return spmv_row_sum_fixed<6, NT>(src, val, e0, x);
+    case 7: return spmv_row_sum_fixed<7, NT>(src, val, e0, x);
+    default: return spmv_row_sum_fixed<8, NT>(src, val, e0, x);
+  }
+}
+// OFFS: the matrix carries offset-coded columns (omask / orec = Csr::off_mask / off_rec): a coded slice takes its columns
+// from them (ColsOffset) and reads no column stream; a slice that is not coded (wave-uniform test of its record) runs the
+// code below as it stands.
+template <int UNR, bool NT, typename COLT = int, bool OFFS = false>
 __global__ __launch_bounds__(256) void k_spmv_sell(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                    const COLT* __restrict__ col, const double* __restrict__ val,
                                                    const double* __restrict__ x, double* __restrict__ y,
-                                                   const int* __restrict__ cbase = nullptr) {
+                                                   const int* __restrict__ cbase = nullptr,
+                                                   const unsigned char* __restrict__ omask = nullptr,
+                                                   const int* __restrict__ orec = nullptr) {
   const int nwb = (nslice + 3) >> 2;            // workgroups (4 slices each)
   const int t = xcd_remap(blockIdx.x, nwb);
   const int s = 4 * t + (threadIdx.x >> 6);
   if (t >= nwb || s >= nslice) return;
   const int l = threadIdx.x & 63;
-  const int64_t a = sl_ptr[s], b = sl_ptr[s + 1];
-  const int4 cb = lp_base_of(cbase, s);       // {b0, b1, ks}: entries k < ks count from b0, the others from b1
+  // OFFS: the slice index is made visibly wave-uniform, so that the slice's pointers, record and bases come through scalar
+  // loads issued together, and the width below selects its case by scalar branches
+  const int su = OFFS ? __builtin_amdgcn_readfirstlane(s) : s;
+  const int64_t a = sl_ptr[su], b = sl_ptr[su + 1];
+  if (OFFS && UNR == 4) {
+    // everything the decision needs is requested before anything is tested: one wait, not one per operand
+    const int rr = 64 * s + l;
+    const unsigned char m = omask[rr];          // in flight with the record and, below, the values
+    const int ov = orec[8 * (int64_t)su + (l & 7)];
+    const int4* rec = reinterpret_cast<const int4*>(orec) + 2 * (int64_t)su;
+    const int4 o0 = rec[0], o1 = rec[1];
+    const int nofix = g_lp_no_fixed;
+    if ((o0.x != OFF_NONE) & (nofix == 0)) {    // coded slices are 1 .. 8 entries wide
+      const ColsOffset src{o0, o1, m, ov, rr, rr < n ? rr : n - 1};
+      const double fs = spmv_row_sum_narrow<NT>((int)((b - a) >> 6), src, val, a + l, x);
+      if (rr < n) y[rr] = fs;
+      return;
+    }
+  }
+  const int4 cb = lp_base_of(cbase, su);      // {b0, b1, ks}: entries k < ks count from b0, the others from b1
   if (UNR == 4 && !g_lp_no_fixed) {           // narrow slice: the two-latency form (same sums, same order)
     const int wd = (int)((b - a) >> 6);
     if (wd >= 1 && wd <= 8) {
-      double fs;
-      switch (wd) {
-        case 1: fs = spmv_row_sum_fixed<1, NT, COLT>(col, val, a + l, cb, x); break;
-        case 2: fs = spmv_row_sum_fixed<2, NT, COLT>(col, val, a + l, cb, x); break;
-        case 3: fs = spmv_row_sum_fixed<3, NT, COLT>(col, val, a + l, cb, x); break;
-        case 4: fs = spmv_row_sum_fixed<4, NT, COLT>(col, val, a + l, cb, x); break;
-        case 5: fs = spmv_row_sum_fixed<5, NT, COLT>(col, val, a + l, cb, x); break;
-        case 6: fs = spmv_row_sum_fixed<6, NT, COLT>(col, val, a + l, cb, x); break;
-        case 7: fs = spmv_row_sum_fixed<7, NT, COLT>(col, val, a + l, cb, x); break;
-        default: fs = spmv_row_sum_fixed<8, NT, COLT>(col, val, a + l, cb, x); break;
-      }
+      const double fs = spmv_row_sum_narrow<NT>(wd, ColsStored<COLT, NT>{col, cb}, val, a + l, x);
       const int rr = 64 * s + l;
       if (rr < n) y[rr] = fs;
       return;
@@ -2238,30 +2320,161 @@ __global__ __launch_bounds__(256) void k_lp_fill(int ns, const int64_t* __restri
     v32[e] = (float)sl_val[e];
   }
 }
+// Offset coding of stencil-like slices (Csr::off_rec / off_mask; read by ColsOffset).  One wave per slice.  A slice of at most
+// 8 entries per row is CODED when the distinct values of col - row over its stored (non-padding: position < row length)
+// entries are at most 8 and every row holds its entries in ascending column order, so that position p of a row is its p-th
+// present offset.  The wave then decodes every position exactly as the kernels will and compares with sl_col: a stored
+// entry must decode to its column, a padding position to a column no higher than the slice's highest stored one (in
+// range whatever the column count of the matrix is).  Anything else leaves the slice on the stored columns (OFF_NONE).
+// cnt[0] += coded slices, cnt[1] += their stored entries (padding included).
+__global__ __launch_bounds__(256) void k_off_code(int ns, int n, const int* __restrict__ rowptr,
+                                                  const int64_t* __restrict__ sl_ptr, const int* __restrict__ sl_col,
+                                                  unsigned char* __restrict__ mask, int* __restrict__ rec,
+                                                  unsigned long long* __restrict__ cnt) {
+  const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= ns) return;
+  const int l = threadIdx.x & 63;
+  const int r = 64 * s + l;
+  const int64_t a = sl_ptr[s];
+  const int wd = (int)((sl_ptr[s + 1] - a) >> 6);
+  int len = r < n ? rowptr[r + 1] - rowptr[r] : 0;
+  bool ok = wd >= 1 && wd <= 8 && __ballot(len > wd) == 0;
+  if (!ok) len = 0;
+  int d[8];
+  int hi = -1;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    d[k] = 0;
+    if (k < len) {
+      const int c = sl_col[a + 64 * (int64_t)k + l];
+      d[k] = c - r;
+      hi = c > hi ? c : hi;
+    }
+  }
+  hi = lp_wave_max(hi);
+  // the sorted distinct offsets, one wave-wide minimum above the last one per round; a ninth one disqualifies the slice
+  int offs[8];
+  int nd = 0, last = OFF_NONE;
+#pragma unroll
+  for (int it = 0; it < 9; ++it) {
+    int mine = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (k < len && d[k] > last && d[k] < mine) mine = d[k];
+    const int m = lp_wave_min(mine);
+    const bool found = m != 0x7fffffff;
+    if (it < 8) {
+      offs[it < 8 ? it : 0] = found ? m : 0;
+      if (found) nd = it + 1;
+    } else if (found) {
+      ok = false;
+    }
+    if (found) last = m;
+  }
+  // presence mask: the slot of every stored entry, strictly ascending with the position
+  unsigned msk = 0;
+  int prev = -1;
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    if (k < len) {
+      int slot = -1;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < nd && offs[j] == d[k]) slot = j;
+      if (slot <= prev) bad = true;
+      else msk |= 1u << slot;
+      prev = slot;
+    }
+  }
+  // decode as ColsOffset does and compare
+  const int pad = r < n ? r : n - 1;
+  unsigned mm = bad ? 0u : msk;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    if (k < wd && ok) {
+      int c = pad;
+      if (mm) {
+        const int slot = __ffs(mm) - 1;
+        int o = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (j == slot) o = offs[j];
+        c = r + o;
+        mm &= mm - 1u;
+      }
+      if (k < len ? c != sl_col[a + 64 * (int64_t)k + l] : (c < 0 || c > hi)) bad = true;
+    }
+  }
+  ok = ok && __ballot(bad) == 0;
+  mask[r] = ok ? (unsigned char)msk : (unsigned char)0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (l == j) rec[8 * (int64_t)s + j] = ok ? offs[j] : OFF_NONE;
+  if (ok && l == 0) {
+    atomicAdd(cnt, 1ull);
+    atomicAdd(cnt + 1, (unsigned long long)wd * 64ull);
+  }
+}
 bool csr_make_lp(Csr& a, const Csr* index_owner) {
   if (spmv_kind() != 1 || a.nslice == 0 || !a.sl_ptr || a.vec_lpr > 0 || a.nlong > 0 || a.lp_val) return a.lp_val != nullptr;
   if (index_owner) {
     if (!index_owner->lp_val || index_owner->sl_col != a.sl_col) return false;
     a.lp_col = index_owner->lp_col;
     a.lp_base = index_owner->lp_base;
+    a.off_mask = index_owner->off_mask;
+    a.off_rec = index_owner->off_rec;
+    a.off_coded = index_owner->off_coded;
+    a.off_nnz = index_owner->off_nnz;
   } else {
     const char* lim_env = getenv("GENEO_LP_SPAN_MAX");       // read per call: tests lower it for one set-up
     int limit = lim_env ? atoi(lim_env) : 65535;
     if (limit < 1 || limit > 65535) limit = 65535;
     a.lp_base = (int*)alloc(sizeof(int4) * (size_t)a.nslice);
-    int* dfail = (int*)alloc(2 * sizeof(int));
-    HIPCHK(hipMemsetAsync(dfail, 0, 2 * sizeof(int), g_stream));
+    // one status block, one read-back: {fail, nsplit} of k_lp_base (two ints), then the two counters of k_off_code
+    unsigned long long* dstat = (unsigned long long*)alloc(3 * sizeof(unsigned long long));
+    HIPCHK(hipMemsetAsync(dstat, 0, 3 * sizeof(unsigned long long), g_stream));
+    int* dfail = (int*)dstat;
+    unsigned long long* dcnt = dstat + 1;
     hipLaunchKernelGGL(k_lp_base, dim3((a.nslice + 3) / 4), dim3(256), 0, g_stream, a.nslice, a.sl_ptr, a.sl_col,
                        (int4*)a.lp_base, dfail, limit, dfail + 1);
-    int hfail[2] = {0, 0};
-    d2h(hfail, dfail, 2 * sizeof(int));
-    dfree(dfail);
+    // the offset coding of the same slices (k_off_code), read back with the span check; it rides on the 16-bit columns,
+    // which the slices that are not coded keep reading.  Not tried where the widths alone rule the 90 % out (M, R, the
+    // coarse levels): slices of at most 8 entries hold at most 8 each, the others at most max_row, so with an average
+    // width W the share of slices wider than 8 is at least (W - 8) / (max_row - 8).
+    const double avg_w = (double)a.sl_nnz / (64.0 * (double)a.nslice);
+    const bool off_try = a.rowptr && (a.max_row <= 8 || avg_w - 8.0 <= 0.1 * ((double)a.max_row - 8.0));
+    if (off_try) {
+      a.off_mask = (unsigned char*)alloc((size_t)64 * (size_t)a.nslice);
+      a.off_rec = (int*)alloc(sizeof(int) * 8 * (size_t)a.nslice);
+      hipLaunchKernelGGL(k_off_code, dim3((a.nslice + 3) / 4), dim3(256), 0, g_stream, a.nslice, a.n, a.rowptr, a.sl_ptr,
+                         a.sl_col, a.off_mask, a.off_rec, dcnt);
+    }
+    unsigned long long hstat[3] = {0, 0, 0};
+    d2h(hstat, dstat, sizeof(hstat));
+    dfree(dstat);
+    int hfail[2];
+    memcpy(hfail, &hstat[0], sizeof(hfail));
+    const unsigned long long* hcnt = hstat + 1;
     if (hfail[0]) {          // a slice needs more than two bases: float values over the 32-bit columns (8 B per entry)
       dfree(a.lp_base);
       a.lp_base = nullptr;
     } else {
       a.lp_col = (unsigned short*)alloc(sizeof(unsigned short) * (size_t)std::max<int64_t>(1, a.sl_nnz));
+      a.off_coded = (int)hcnt[0];
+      a.off_nnz = (int64_t)hcnt[1];
     }
+    // the coded kernels pay a branch per slice: they run only where at least 90 % of the slices are coded
+    const bool off_use = a.lp_col && a.off_coded > 0 && 10 * (int64_t)a.off_coded >= 9 * (int64_t)a.nslice;
+    if (!off_use) {
+      dfree(a.off_mask);
+      dfree(a.off_rec);
+      a.off_mask = nullptr;
+      a.off_rec = nullptr;
+    }
+    if (getenv("GENEO_DEBUG"))
+      fprintf(stderr, "[offsets] %d-row matrix, %d slices, %d coded%s\n", a.n, a.nslice, a.off_coded,
+              !off_try ? " (too wide: not tried)" : off_use ? "" : (a.off_coded ? " (under 90 %: stored columns kept)" : ""));
     if (getenv("GENEO_DEBUG") && (hfail[0] || hfail[1]))
       fprintf(stderr, "[lp] %d-row matrix, %d slices: %s (span limit %d)\n", a.n, a.nslice,
               hfail[0] ? "32-bit columns kept (a slice needs more than two bases)"
@@ -2279,17 +2492,19 @@ bool csr_make_lp(Csr& a, const Csr* index_owner) {
 // run time IS that chain (0.46-0.54 of the HBM peak while the FP64 SpMV on the same pattern reaches
 // 0.72).  The products are summed exactly as that loop sums them (KW / 4 rounds into four accumulators, the remainder
 // into the first): results are bit-identical.
-template <int KW, int EPI, typename COLT, bool NT>
-__device__ __forceinline__ double lp_row_sum_fixed(const COLT* __restrict__ col, const float* __restrict__ val, int64_t e0,
-                                                   const int4 cb, const double* __restrict__ xin,
-                                                   const double* __restrict__ cs) {
+// SRC: where the columns come from (ColsStored: the stored stream; ColsOffset: an offset-coded slice), as in
+// spmv_row_sum_fixed.
+template <int KW, int EPI, bool NT, typename SRC>
+__device__ __forceinline__ double lp_row_sum_fixed(const SRC& src, const float* __restrict__ val, int64_t e0,
+                                                   const double* __restrict__ xin, const double* __restrict__ cs) {
   int c[KW];
   double v[KW];
 #pragma unroll
   for (int u = 0; u < KW; ++u) {
-    c[u] = (u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e0 + 64 * u) : col[e0 + 64 * u]);
+    c[u] = src.at(u, e0);
     v[u] = (double)(NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u]);
   }
+  src.template finish<KW>(c);
   double xv[KW];
 #pragma unroll
   for (int u = 0; u < KW; ++u) xv[u] = (EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]];
@@ -2340,17 +2555,35 @@ __device__ __forceinline__ double lp_row_sum_p16(const COLT* __restrict__ col, c
   }
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
+template <int EPI, bool NT, typename SRC>
+__device__ __forceinline__ double lp_row_sum_narrow(int wd, const SRC& src, const float* __restrict__ val, int64_t e0,
+                                                    const double* __restrict__ xin, const double* __restrict__ cs) {
+  switch (wd) {
+    case 1: return lp_row_sum_fixed<1, EPI, NT>(src, val, e0, xin, cs);
+    case 2: return lp_row_sum_fixed<2, EPI, NT>(src, val, e0, xin, cs);
+    case 3: return lp_row_sum_fixed<3, EPI, NT>(src, val, e0, xin, cs);
+    case 4: return lp_row_sum_fixed<4, EPI, NT>(src, val, e0, xin, cs);
+    case 5: return lp_row_sum_fixed<5, EPI, NT>(src, val, e0, xin, cs);
+    case 6: return lp_row_sum_fixed<6, EPI, NT>(src, val, e0, xin, cs);
+    case 7: return lp_row_sum_fixed<7, EPI, NT>(src, val, e0, xin, cs);
+    default: return lp_row_sum_fixed<8, EPI, NT>(src, val, e0, xin, cs);
+  }
+}
 // WPS = 1: one wave per slice (four slices per workgroup), WPS = 4: one workgroup per slice (wide slices), as the FP64
 // kernels k_spmv_sell_epi / k_spmv_sell_wide above; summation order fixed.
 // NT: the once-read (col, val) stream of a LARGE companion is marked non-temporal, as in k_spmv_sell (the vectors of the
 // cycle, not the matrix, are what the caches should keep); a hint only -- same loads, same arithmetic.
-template <int EPI, int WPS, typename COLT, bool NT>
+// OFFS (WPS = 1 only): the matrix carries offset-coded columns (omask / orec, see k_spmv_sell): coded slices read no column
+// stream, the others run today's code.
+template <int EPI, int WPS, typename COLT, bool NT, bool OFFS = false>
 __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                       const COLT* __restrict__ col, const float* __restrict__ val,
                                                       const int* __restrict__ base, const double* __restrict__ x,
                                                       double* __restrict__ y, const double* __restrict__ b,
                                                       double* __restrict__ z, const double* __restrict__ dinv, double w,
-                                                      const double* __restrict__ cs) {
+                                                      const double* __restrict__ cs,
+                                                      const unsigned char* __restrict__ omask = nullptr,
+                                                      const int* __restrict__ orec = nullptr) {
   constexpr int UNR = 4;
   __shared__ double part[3][64];
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -2364,8 +2597,18 @@ __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict_
     s = xcd_remap(blockIdx.x, nslice);
     if (s >= nslice) return;
   }
-  const int64_t a = sl_ptr[s], e1 = sl_ptr[s + 1];
-  const int4 cb = lp_base_of(base, s);   // 16-bit columns are offsets from the slice's bases (k_lp_base)
+  // OFFS: the slice index made visibly wave-uniform -- scalar loads of the slice's pointers, record and bases (see k_spmv_sell)
+  const int su = (OFFS && WPS == 1) ? __builtin_amdgcn_readfirstlane(s) : s;
+  const int64_t a = sl_ptr[su], e1 = sl_ptr[su + 1];
+  const int4 cb = lp_base_of(base, su);  // 16-bit columns are offsets from the slice's bases (k_lp_base)
+  int4 o0 = int4{OFF_NONE, 0, 0, 0}, o1 = int4{0, 0, 0, 0};
+  int nofix = 0;
+  if (OFFS && WPS == 1) {                // requested with the pointers and the bases: one wait for all of them
+    const int4* rec = reinterpret_cast<const int4*>(orec) + 2 * (int64_t)su;
+    o0 = rec[0];
+    o1 = rec[1];
+    nofix = g_lp_no_fixed;
+  }
   const double* __restrict__ xin = (EPI == EPI_PRE) ? b : x;
   // The epilogue's own operands do not depend on the product: their loads are issued HERE, in front of the matrix stream,
   // instead of after the last gather has come back (one dependent memory round trip less per wave; a wave holds one
@@ -2373,6 +2616,12 @@ __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict_
   const int r = 64 * s + l;
   const bool rok = r < n && (WPS == 1 || wv == 0);
   double e_b = 0.0, e_z = 0.0, e_d = 0.0, e_x = 0.0;
+  unsigned char om = 0;
+  int oov = 0;
+  if (OFFS && WPS == 1) {                 // the presence mask and the offsets by lane: first in the queue, the decode waits for them alone
+    om = omask[r];
+    oov = orec[8 * (int64_t)su + (l & 7)];
+  }
   if (rok) {
     if (EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE) e_b = b[r];
     if (EPI == EPI_ADD || EPI == EPI_POST) e_z = z[r];
@@ -2387,21 +2636,16 @@ __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict_
   int k = (WPS == 1 ? 0 : wv);            // entry index of e within its row
   const int wd = (int)((e1 - a) >> 6);    // entries per row of this slice (wave-uniform)
   double fixed_sum = 0.0;
-  const bool fixed = (WPS == 1 && wd >= 1 && wd <= 16 && !g_lp_no_fixed);
-  if (fixed && wd > 8) {
+  const bool fixed = (WPS == 1 && wd >= 1 && wd <= 16 && !((OFFS && WPS == 1) ? nofix : g_lp_no_fixed));
+  const bool coded = OFFS && fixed && o0.x != OFF_NONE;   // coded slices are 1 .. 8 entries wide
+  if (coded) {
+    fixed_sum = lp_row_sum_narrow<EPI, NT>(wd, ColsOffset{o0, o1, om, oov, r, r < n ? r : n - 1}, val, e, xin, cs);
+    e = e1;
+  } else if (fixed && wd > 8) {
     fixed_sum = lp_row_sum_p16<EPI, COLT, NT>(col, val, e, wd, cb, xin, cs);
     e = e1;
   } else if (fixed) {
-    switch (wd) {
-      case 1: fixed_sum = lp_row_sum_fixed<1, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 2: fixed_sum = lp_row_sum_fixed<2, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 3: fixed_sum = lp_row_sum_fixed<3, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 4: fixed_sum = lp_row_sum_fixed<4, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 5: fixed_sum = lp_row_sum_fixed<5, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 6: fixed_sum = lp_row_sum_fixed<6, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      case 7: fixed_sum = lp_row_sum_fixed<7, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-      default: fixed_sum = lp_row_sum_fixed<8, EPI, COLT, NT>(col, val, e, cb, xin, cs); break;
-    }
+    fixed_sum = lp_row_sum_narrow<EPI, NT>(wd, ColsStored<COLT, NT>{col, cb}, val, e, xin, cs);
     e = e1;                               // nothing left for the general loops below
   }
   for (; e + STEP * (UNR - 1) < e1; e += STEP * UNR, k += WPS * UNR) {
@@ -2451,9 +2695,12 @@ static void spmv_lp_launch(const Csr& a, const double* x, double* y, const doubl
   // of companion entries).  Algorithmic bytes: 6 per stored entry (float value + 16-bit column; 8 when the slice spans
   // more than 65535 columns) + 4 per slice + 8 per row and vector the epilogue streams (x or b in, y out, plus z / r).
   constexpr int nvec = EPI == EPI_NONE ? 2 : (EPI == EPI_POST ? 5 : (EPI == EPI_JAC ? 4 : 3));
+  // Offset-coded slices stream no columns: 4 per stored entry + 64 mask bytes + a 32-byte record per slice.
   const double ebytes = a.lp_col ? 6.0 : 8.0;
-  ProfScope prof(PROF_LP, (double)a.sl_nnz * ebytes >= 32e6, (double)a.sl_nnz * ebytes + 4.0 * a.nslice + 8.0 * nvec * (double)a.n,
-                 2.0 * (double)a.nnz);
+  const bool offs = g_sell_offsets && a.off_mask && a.off_rec && a.lp_col && !sell_wide(a);
+  const double obytes = offs ? 96.0 * a.off_coded - 2.0 * (double)a.off_nnz : 0.0;
+  ProfScope prof(PROF_LP, (double)a.sl_nnz * ebytes >= 32e6,
+                 (double)a.sl_nnz * ebytes + obytes + 4.0 * a.nslice + 8.0 * nvec * (double)a.n, 2.0 * (double)a.nnz);
   const double* cs = (EPI == EPI_PRE && !a.col_scaled) ? dinv : nullptr;
   const int per = (a.nslice + 7) / 8;
   const int perw = ((a.nslice + 3) / 4 + 7) / 8;
@@ -2471,7 +2718,14 @@ static void spmv_lp_launch(const Csr& a, const double* x, double* y, const doubl
     if (a.lp_col) LP_LAUNCH(4, unsigned short, a.lp_col, per * 8);
     else LP_LAUNCH(4, int, a.sl_col, per * 8);
   } else {
-    if (a.lp_col) LP_LAUNCH(1, unsigned short, a.lp_col, perw * 8);
+    if (offs) {
+      if (nt)
+        hipLaunchKernelGGL((k_spmv_sell_lp<EPI, 1, unsigned short, true, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
+                           a.nslice, a.n, a.lp_col, a.lp_val, a.lp_base, x, y, b, z, dinv, w, cs, a.off_mask, a.off_rec);
+      else
+        hipLaunchKernelGGL((k_spmv_sell_lp<EPI, 1, unsigned short, false, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
+                           a.nslice, a.n, a.lp_col, a.lp_val, a.lp_base, x, y, b, z, dinv, w, cs, a.off_mask, a.off_rec);
+    } else if (a.lp_col) LP_LAUNCH(1, unsigned short, a.lp_col, perw * 8);
     else LP_LAUNCH(1, int, a.sl_col, perw * 8);
   }
 #undef LP_LAUNCH
@@ -2595,6 +2849,21 @@ void spmv(const Csr& a, const double* x, double* y) {
     // 42.2 us without; back-to-back re-reads of the same matrix (a micro-benchmark, not the solver's
     // access pattern) prefer the cached stream, which is why small (coarse-level) matrices keep it.
     int variant = g_sell_variant;
+    if (variant == 0 && g_sell_offsets && a.off_mask && a.off_rec && a.lp_col && a.lp_base) {
+      // offset-coded columns: 8 B per entry + 1.5 B per row in the coded slices, the 16-bit stream in the others; the
+      // accumulation order of the default kernel (the paths agree to the bit).  A change of dispatch for SMALL coded
+      // matrices too: below the sell_nt size they used to run <4, false, int> on the 32-bit columns (the 16-bit FP64 form was
+      // for large matrices only); their few slices that are not coded now read lp_col -- same entries, same order, same sums.
+      if (sell_nt(a))
+        hipLaunchKernelGGL((k_spmv_sell<4, true, unsigned short, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
+                           a.nslice, a.n, a.lp_col, a.sl_val, x, y, a.lp_base, a.off_mask, a.off_rec);
+      else
+        hipLaunchKernelGGL((k_spmv_sell<4, false, unsigned short, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
+                           a.nslice, a.n, a.lp_col, a.sl_val, x, y, a.lp_base, a.off_mask, a.off_rec);
+      if (a.nlong > 0)
+        hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val, x, y);
+      return;
+    }
     if ((variant == 0 || variant >= 5) && a.lp_col && a.lp_base && sell_nt(a)) {   // 16-bit column offsets are available: 10 B per entry
       // Default: 4 steps in flight + one-at-a-time tail (the same accumulation order as the 32-bit-column kernel: the two
       // paths agree to the bit).  GENEO_SELL_VARIANT=5 / 7: the predicated eight-step form (round-3 experiment: 20 % faster
@@ -4998,6 +5267,7 @@ bool set_variant(const char* name, int value) {
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lp_no_fixed), &off, sizeof(int)));
     return true;
   }
+  if (k == "sell_offsets") { g_sell_offsets = value != 0; return true; }
   if (k == "spgemm_small_rows") {
     lazy_init();
     const int off = value ? 0 : 1;

@@ -682,6 +682,13 @@ PetscErrorCode GeneoSpmvFusedSingle(GeneoSpmv h, int epi, const double* X, doubl
   return 0;
 }
 
+PetscErrorCode GeneoSpmvOffsetInfo(GeneoSpmv h, int* slices, int* coded) {
+  if (!h) return 1;
+  if (slices) *slices = h->a.nslice;
+  if (coded) *coded = h->a.off_coded;
+  return 0;
+}
+
 // test hook for the device sparse products: op 0: C = A B, op 1: C = A^T (B ignored).  Returns nnz(C) (-1: a row
 // exceeded the kernels' capacity, -2: error); fills the outputs when cap >= nnz (rowptr_out has C's rows + 1 entries).
 long long GeneoTestSparseProduct(int op, const GeneoCsr* A, const GeneoCsr* B, int ncols, int* rowptr_out, int* col_out,

@@ -389,6 +389,13 @@ class Spmv:
             raise GenEOError(self.lib.PCGenEOGetError(None).decode())
         return yd.to_host(), (zd.to_host() if zd is not None else None)
 
+    def offset_info(self):
+        """(slices, coded slices) of the offset coding of the columns (made with the companion: after fused_single)."""
+        ns, nc = C.c_int(0), C.c_int(0)
+        if self.lib.GeneoSpmvOffsetInfo(self.h, C.byref(ns), C.byref(nc)):
+            raise GenEOError("GeneoSpmvOffsetInfo failed")
+        return ns.value, nc.value
+
     def algorithmic_bytes(self):
         """nnz*(8+4) + (n+1)*4 + n*8 (x once) + n*8 (y)."""
         return self.nnz * 12 + (self.n + 1) * 4 + self.n * 16

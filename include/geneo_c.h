@@ -349,6 +349,9 @@ PetscErrorCode GeneoSpmmDualResidualTest(GeneoSpmv a, GeneoSpmv b, const double*
                                          int m, int nsub, const int* suboff, const double* lam, const double* mask);
 PetscErrorCode GeneoSpmvFusedSingle(GeneoSpmv h, int epi, const double* X_dev, double* Y_dev, const double* B_dev,
                                     double* Z_dev, const double* dinv_dev, double w);
+/* what the offset coding of the columns found on the matrix (made with the single-precision companion, i.e. by the first
+ * GeneoSpmvFusedSingle): its 64-row slices, and how many of them are coded (0 on a backend without the coded kernels) */
+PetscErrorCode GeneoSpmvOffsetInfo(GeneoSpmv h, int* slices, int* coded);
 /* device sparse products of the multigrid set-up (test hook): op 0: C = A B, op 1: C = A^T; returns nnz(C), -1 when a
  * row exceeds the kernels' per-row capacity (callers fall back to the host product), -2 on error */
 long long GeneoTestSparseProduct(int op, const GeneoCsr* A, const GeneoCsr* B, int ncols, int* rowptr_out, int* col_out,
