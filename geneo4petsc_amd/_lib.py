@@ -163,6 +163,10 @@ SYMBOLS = {
     "GeneoBlockKernel": (C.c_int, [C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p,
                                    C.c_int, c_dbl_p]),
     "GeneoTestPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
+    "PCGenEOGetCoarseInfo": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "GeneoTestCoarseFactor": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
+    "GeneoTestCoarseSolve": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int]),
+    "GeneoTestCoarseElapsed": (C.c_int, [c_dbl_p, c_dbl_p]),
     "GeneoTestCgSteps": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 + [c_dbl_p]),
     "GeneoTestCsrOp": (C.c_longlong, [C.c_int, C.POINTER(GeneoCsr), C.POINTER(GeneoCsr), c_int_p, c_dbl_p, C.POINTER(C.c_void_p),
                        c_int_p, c_int_p, c_dbl_p, C.c_longlong]),

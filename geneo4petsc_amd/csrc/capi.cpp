@@ -9,8 +9,14 @@
 #include <string>
 #include <vector>
 
+#include <algorithm>
+#include <chrono>
+#include <thread>
+
 #include "../../include/geneo_c.h"
+#include "coarse_dev.h"
 #include "core.h"
+#include "dense.h"
 
 struct _p_GeneoPC {
   geneo::PC* ctx = nullptr;   // pc->data in PETSc (src/geneo.cpp:2645)
@@ -155,6 +161,11 @@ const char* usageGenEO_c(void) {
          "                     - check partition of unity\n"
          "                     - check matrices are SPD (check.SPD.A.log, check<id>.SPD.<pb>.B.log)\n"
          "                     - check R from Z=QR (check<id>.setup.Z.R, check.setup.ZE2G.R)\n"
+         "  -geneo_coarse_device auto|never|always   where the coarse operator E is factored and solved (defaults to auto)\n"
+         "                   never:  host Cholesky; sweeps in one workgroup up to dimE 1024, on the host above\n"
+         "                   auto:   as never up to dimE 1024; above: blocked factorisation and sweeps on the GPU\n"
+         "                   always: the blocked GPU kernels at any dimE (host sequence when E is not positive definite)\n"
+         "  -geneo_coarse_block B   block size of the blocked kernels, a multiple of 16 in 16 .. 256 (defaults to 128)\n"
          "  -geneo_nicolaides_zero X   the Nicolaides rule takes min(lambda) >= X eps as 'no zero eigenvalue found'\n"
          "                   (1 = the reference's literal test; defaults to 100)\n"
          "  -geneo_eig_group_rows R / -geneo_eig_mem_gb G   memory-bounded set-up: eigensolve the rank's subdomains in\n"
@@ -392,6 +403,12 @@ int PCGenEOGetLocalDims(PC pc, int* k, int cap) {
   const auto& v = pc->ctx->ksub_global;
   for (int i = 0; i < (int)v.size() && i < cap; ++i) k[i] = v[i];
   return (int)v.size();
+}
+
+PetscErrorCode PCGenEOGetCoarseInfo(PC pc, int* dimE, int* factor_on_device, int* solve_kind, int* block) {
+  if (!pc || !pc->ctx) return 1;
+  pc->ctx->coarse_info(dimE, factor_on_device, solve_kind, block);
+  return 0;
 }
 
 // ---- getInput plugin ABI (driver:75-96) -----------------------------------------------------------
@@ -868,6 +885,143 @@ int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* co
   }
   if (have_chunks) bk::chunks_free(c);
   return rc;
+}
+
+// ---- test hooks of the blocked coarse kernels (coarse_dev.h; tests/test_gpu_coarse_device.py) ---------------------------
+// Host arrays in and out.  Every device buffer is allocated with CANARY_PAD doubles (ints for the status word) in front and
+// behind, filled with a canary pattern, and read back whole: a broken canary or a changed input is an error (-1).
+// nb == 0 runs what the PC does without these kernels instead -- dense::cholesky_blocked and the transposition; the download,
+// dense::cholesky_solve_lu and the upload -- so that the two can be timed and compared by one caller.
+namespace {
+static constexpr size_t CANARY_PAD = 64;
+static const double kCanary = -6.02214076e+231;
+static const int kCanaryInt = 0x5ca1ab1e;
+static double g_coarse_factor_ms = -1.0, g_coarse_solve_ms = -1.0;
+
+struct PaddedBuf {          // device buffer of n doubles between two canary pads
+  double* d = nullptr;
+  size_t n = 0;
+  std::vector<double> h;
+  PaddedBuf(size_t n_, const double* src) : n(n_), h(n_ + 2 * CANARY_PAD, kCanary) {
+    if (src) std::copy(src, src + n, h.begin() + CANARY_PAD);
+    d = (double*)bk::alloc(sizeof(double) * h.size());
+    bk::h2d(d, h.data(), sizeof(double) * h.size());
+  }
+  ~PaddedBuf() { bk::dfree(d); }
+  double* ptr() { return d + CANARY_PAD; }
+  // reads the buffer back; throws when a pad was written (or, with `same`, when the payload differs from it)
+  const double* fetch(const char* what, const double* same = nullptr) {
+    bk::d2h(h.data(), d, sizeof(double) * h.size());
+    for (size_t i = 0; i < CANARY_PAD; ++i)
+      if (std::memcmp(&h[i], &kCanary, 8) || std::memcmp(&h[CANARY_PAD + n + i], &kCanary, 8))
+        throw std::runtime_error(std::string("coarse test hook: write outside ") + what);
+    if (same && n && std::memcmp(h.data() + CANARY_PAD, same, sizeof(double) * n))
+      throw std::runtime_error(std::string("coarse test hook: input changed: ") + what);
+    return h.data() + CANARY_PAD;
+  }
+};
+double wall_ms(std::chrono::steady_clock::time_point a) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+}
+}  // namespace
+
+int GeneoTestCoarseFactor(int n, int nb, const double* E, double* L, double* LT, int* status) {
+  try {
+    if (n < 0 || !E || !L || !LT || !status) throw std::runtime_error("GeneoTestCoarseFactor: bad arguments");
+    const size_t nn = (size_t)n * n;
+    if (nb == 0) {     // the host factorisation of PC::build_E
+      std::vector<double> a(E, E + nn);
+      const auto t0 = std::chrono::steady_clock::now();
+      const bool ok = dense::cholesky_blocked(a, n, (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+      std::fill(LT, LT + nn, 0.0);
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) LT[(size_t)j * n + i] = a[(size_t)i * n + j];
+      g_coarse_factor_ms = wall_ms(t0);
+      for (int i = 0; i < n; ++i)       // the host routine leaves E above the diagonal, where nothing of the PC reads
+        std::fill(a.begin() + (size_t)i * n + i + 1, a.begin() + (size_t)(i + 1) * n, 0.0);
+      std::copy(a.begin(), a.end(), L);
+      *status = ok ? 0 : n;      // the host routine keeps no pivot index
+      return 0;
+    }
+    PaddedBuf dE(nn, E), dL(nn, nullptr), dLT(nn, nullptr);
+    std::vector<int> hs(1 + 2 * CANARY_PAD, kCanaryInt);
+    int* dst = (int*)bk::alloc(sizeof(int) * hs.size());
+    bk::h2d(dst, hs.data(), sizeof(int) * hs.size());
+    void* e0 = bk::event_create();
+    void* e1 = bk::event_create();
+    bk::event_record(e0);
+    const bool have = bk::coarse_factor(dE.ptr(), n, nb, dL.ptr(), dLT.ptr(), dst + CANARY_PAD);
+    bk::event_record(e1);
+    if (have) {
+      g_coarse_factor_ms = (double)bk::event_elapsed_ms(e0, e1);
+      bk::d2h(hs.data(), dst, sizeof(int) * hs.size());
+    }
+    bk::event_destroy(e0);
+    bk::event_destroy(e1);
+    bk::dfree(dst);
+    if (!have) return -3;
+    for (size_t i = 0; i < CANARY_PAD; ++i)
+      if (hs[i] != kCanaryInt || hs[CANARY_PAD + 1 + i] != kCanaryInt)
+        throw std::runtime_error("coarse test hook: write outside the status word");
+    *status = hs[CANARY_PAD];
+    dE.fetch("E", E);
+    std::copy_n(dL.fetch("L"), nn, L);
+    std::copy_n(dLT.fetch("LT"), nn, LT);
+    return 0;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -1;
+  }
+}
+
+int GeneoTestCoarseSolve(int n, int nb, const double* L, const double* LT, double* y, int reps) {
+  try {
+    if (n < 0 || !L || !LT || !y || reps < 1) throw std::runtime_error("GeneoTestCoarseSolve: bad arguments");
+    const size_t nn = (size_t)n * n;
+    PaddedBuf dy0(n, y), dy(n, nullptr);
+    if (nb == 0) {     // the host round trip of PC::coarse_solve_local
+      const std::vector<double> l(L, L + nn), u(LT, LT + nn);
+      std::vector<double> hy(std::max(1, n));
+      const auto t0 = std::chrono::steady_clock::now();
+      for (int r = 0; r < reps; ++r) {
+        bk::d2h(hy.data(), dy0.ptr(), sizeof(double) * n);
+        dense::cholesky_solve_lu(l, u, n, hy.data());
+        bk::h2d(dy.ptr(), hy.data(), sizeof(double) * n);
+      }
+      bk::sync();
+      g_coarse_solve_ms = wall_ms(t0) / reps;
+      std::copy_n(dy.fetch("y"), n, y);
+      return 0;
+    }
+    PaddedBuf dL(nn, L), dLT(nn, LT);
+    void* e0 = bk::event_create();
+    void* e1 = bk::event_create();
+    bool have = true;
+    bk::event_record(e0);
+    for (int r = 0; r < reps && have; ++r) {   // every repetition solves the caller's y again
+      bk::d2d(dy.ptr(), dy0.ptr(), sizeof(double) * n);
+      have = bk::coarse_solve(dL.ptr(), dLT.ptr(), n, nb, dy.ptr());
+    }
+    bk::event_record(e1);
+    if (have) g_coarse_solve_ms = (double)bk::event_elapsed_ms(e0, e1) / reps;
+    bk::event_destroy(e0);
+    bk::event_destroy(e1);
+    if (!have) return -3;
+    dL.fetch("L", L);
+    dLT.fetch("LT", LT);
+    dy0.fetch("y (input copy)", y);
+    std::copy_n(dy.fetch("y"), n, y);
+    return 0;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -1;
+  }
+}
+
+int GeneoTestCoarseElapsed(double* factor_ms, double* solve_ms) {
+  if (factor_ms) *factor_ms = g_coarse_factor_ms;
+  if (solve_ms) *solve_ms = g_coarse_solve_ms;
+  return 0;
 }
 
 // The batched CG of the local solves on the matrix of `h` (rows 0 .. suboff[nsub]): cg_start, then `iters` times

@@ -35,7 +35,15 @@
 #include <thread>
 
 #include "amg.h"
+#include "coarse_dev.h"
 #include "dense.h"
+
+// A backend without the blocked coarse kernels (coarse_dev.h) links these: "not available", nothing touched.  The HIP
+// object's definitions take their place in the product library.
+namespace bk {
+__attribute__((weak)) bool coarse_factor(const double*, int, int, double*, double*, int*) { return false; }
+__attribute__((weak)) bool coarse_solve(const double*, const double*, int, int, double*) { return false; }
+}  // namespace bk
 
 namespace geneo {
 
@@ -167,6 +175,20 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
     o.dls1_amg_single = (value == "single");
     return "";
   }
+  if (key == "-geneo_coarse_device") {
+    if (value == "auto") o.coarse_device = Options::COARSE_AUTO;
+    else if (value == "never") o.coarse_device = Options::COARSE_NEVER;
+    else if (value == "always") o.coarse_device = Options::COARSE_ALWAYS;
+    else return "unsupported -geneo_coarse_device " + value;
+    return "";
+  }
+  if (key == "-geneo_coarse_block") {
+    int v;
+    if (!to_int(value, v) || v < 16 || v > 256 || v % 16 != 0)
+      return "invalid option -geneo_coarse_block, " + value + " is not a multiple of 16 in 16 .. 256";
+    o.coarse_block = v;
+    return "";
+  }
   if (key == "-amg_coarse_size") return integer(o.amg_coarse_size);
   if (key == "-amg_smooth_degree") return integer(o.amg_smooth_degree);
   if (key == "-amg_smooth_ratio") return dbl(o.amg_smooth_ratio);
@@ -259,6 +281,8 @@ void PC::free_all() {
   d_D = d_dinv1 = d_dinvN = d_xe = d_ye = d_xL = d_wL = nullptr;
   d_cg_r = d_cg_z = d_cg_p = d_cg_q = d_cg_sc = d_t1 = d_t2 = d_t3 = d_x0 = d_scal = d_rvtmp = nullptr;
   d_Z = nullptr; d_zbase = nullptr; d_ksub = d_zoff = d_subgid = nullptr; d_yE = nullptr; d_EL = d_ELT = nullptr;
+  E_dev = false;
+  E_nb = 0;
   is_setup = false;
 }
 
@@ -1268,8 +1292,11 @@ void PC::coarse_solve_local(const double* xL, double* yE) {
   auto t1 = clk::now();
   // E^-1 (geneo.cpp:1493, KSPSolve(pcKSPL2)): the replicated Cholesky factor lives on the device and the two triangular
   // sweeps are one launch behind the all-reduce -- no download, host solve, upload and no host synchronisation in the
-  // preconditioner application.  Host path: E not positive definite to rounding (LU with pivoting) or dimE > 1024.
-  if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
+  // preconditioner application.  A factor made on the device (build_E) takes the blocked sweeps, at any dimE, stream-ordered
+  // in the same way.  Host path: E not positive definite to rounding (LU with pivoting), or dimE > 1024 with a host factor.
+  if (E_dev) {
+    if (!bk::coarse_solve(d_EL, d_ELT, dimE, E_nb, yE)) throw std::runtime_error("GenEO - solve KO: dcs2 (no blocked coarse sweeps on this backend)");
+  } else if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
     bk::d2h(h_yE.data(), yE, sizeof(double) * dimE);
     if (E_chol) dense::cholesky_solve_lu(Efac, EfacT, dimE, h_yE.data());
     else dense::lu_solve(Efac, dimE, Epiv, h_yE.data());
@@ -3258,6 +3285,14 @@ int PC::build_E() {
   for (int a = 0; a < dimE; ++a)
     for (int b = a + 1; b < dimE; ++b) Efac[(size_t)a * dimE + b] = Efac[(size_t)b * dimE + a] =
         0.5 * (Efac[(size_t)a * dimE + b] + Efac[(size_t)b * dimE + a]);
+  const bool want_dev = dimE > 0 && (opt.coarse_device == Options::COARSE_ALWAYS ||
+                                     (opt.coarse_device == Options::COARSE_AUTO && dimE > 1024));
+  if (want_dev && factor_E_on_device(Efac)) {   // L and L^T stay on the device: nothing on the host reads the factor
+    E_chol = true;
+    Efac.clear();
+    EfacT.clear();
+    return 0;
+  }
   std::vector<double> sym = Efac;
   E_chol = dense::cholesky_blocked(Efac, dimE, (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
   if (E_chol) {   // U = L^T next to L: the backward substitution then walks contiguous rows too
@@ -3265,7 +3300,7 @@ int PC::build_E() {
     for (int a = 0; a < dimE; ++a)
       for (int b = 0; b <= a; ++b) EfacT[(size_t)b * dimE + a] = Efac[(size_t)a * dimE + b];
   }
-  if (E_chol && dimE > 0 && dimE <= 1024) {     // the factor, twice, for the device sweeps of coarse_solve_local
+  if (E_chol && dimE > 0 && dimE <= 1024 && !want_dev) {     // the factor, twice, for the device sweeps of coarse_solve_local
     d_EL = (double*)bk::alloc(sizeof(double) * Efac.size());
     d_ELT = (double*)bk::alloc(sizeof(double) * EfacT.size());
     bk::h2d(d_EL, Efac.data(), sizeof(double) * Efac.size());
@@ -3276,6 +3311,48 @@ int PC::build_E() {
     if (!dense::lu_factor(Efac, dimE, Epiv)) return fail("GenEO - solve KO: dcs2 (singular coarse operator E)");
   }
   return 0;
+}
+
+// The symmetrised E, uploaded and factored by the blocked device kernels (coarse_dev.h).  One read of the status word is
+// the only synchronisation.  false -- the backend has no such kernels, a pivot was not positive, or the device memory
+// could not be had -- leaves nothing behind: build_E then runs the host sequence.
+bool PC::factor_E_on_device(const std::vector<double>& sym) {
+  double *dL = nullptr, *dLT = nullptr;
+  int* dst = nullptr;
+  bool ok = false;
+  try {
+    const size_t bytes = sizeof(double) * sym.size();
+    dL = (double*)bk::alloc(bytes);
+    dLT = (double*)bk::alloc(bytes);
+    dst = (int*)bk::alloc(sizeof(int));
+    bk::h2d(dL, sym.data(), bytes);
+    if (bk::coarse_factor(dL, dimE, opt.coarse_block, dL, dLT, dst)) {
+      int st = -1;
+      bk::d2h(&st, dst, sizeof(int));
+      ok = (st == 0);
+    }
+  } catch (std::exception&) {
+    ok = false;
+  }
+  bk::dfree(dst);
+  if (!ok) {
+    bk::dfree(dL);
+    bk::dfree(dLT);
+    return false;
+  }
+  d_EL = dL;
+  d_ELT = dLT;
+  E_dev = true;
+  E_nb = opt.coarse_block;
+  return true;
+}
+
+// solve_kind: 0 host round trip, 1 one-workgroup sweeps (bk::chol_solve), 2 blocked sweeps (bk::coarse_solve)
+void PC::coarse_info(int* dim, int* factor_on_device, int* solve_kind, int* block) const {
+  if (dim) *dim = dimE;
+  if (factor_on_device) *factor_on_device = E_dev ? 1 : 0;
+  if (solve_kind) *solve_kind = E_dev ? 2 : ((E_chol && d_EL && dimE <= 1024) ? 1 : 0);
+  if (block) *block = E_dev ? E_nb : 0;
 }
 
 // ------------------------------------------------------------------------------------ Krylov

@@ -80,6 +80,16 @@ struct Options {
   // test at -els2_eps_tol, and a different ruler moves the outer iteration count at the loose tolerance of the benchmark
   // (126^3: 25 -> 23) away from the reference-literal oracle's.
   double dls1_amg_strength = 0.04, els2_amg_strength = 0.0;
+  // -geneo_coarse_device auto|never|always: where the replicated coarse operator E is factored and solved.
+  //   never:  host Cholesky (LU when that fails); sweeps in one workgroup up to dimE 1024, on the host above
+  //   auto:   as never up to dimE 1024; above: blocked device factorisation and blocked device sweeps (coarse_dev.h)
+  //   always: the blocked device kernels at any dimE > 0
+  // Whenever the device factorisation is not to be had (backend without the kernels, E not positive definite to rounding,
+  // no device memory) the host sequence runs instead, with the host round trip in the apply.
+  // -geneo_coarse_block nb: block size of those kernels, a multiple of 16 in 16 .. 256
+  enum CoarseDevice { COARSE_AUTO = 0, COARSE_NEVER = 1, COARSE_ALWAYS = 2 };
+  int coarse_device = COARSE_AUTO;
+  int coarse_block = 128;   // within 7 % of the best sweeps and 1.5 x of the best factor time at 1256 .. 5120
   bool dls1_amg_single = true;   // -dls1_amg_precision single|double: storage of the level matrices the V-cycle of the local solves reads
   // Krylov driver (counterpart of the PETSc KSP the reference calls at driver:1240)
   std::string ksp_type = "gmres";
@@ -154,6 +164,8 @@ class PC {
   int setup(const double* b_dev);                       // setUpGenEOPC, geneo.cpp:1672
   int apply(const double* x_dev, double* y_dev);        // applyGenEOPC, geneo.cpp:2051
   int apply_q(const double* x_dev, double* y_dev);      // applyQ, geneo.cpp:1435
+  // where E was factored and how E^-1 is applied (PCGenEOGetCoarseInfo)
+  void coarse_info(int* dim, int* factor_on_device, int* solve_kind, int* block) const;
   int matmult(const double* x_dev, double* y_dev);      // MatMult(MATIS)
   int solve(const double* b_dev, double* x_dev, KspResult* res);  // KSPSolve counterpart
   int n_owned() const { return (int)owned.size(); }
@@ -191,6 +203,9 @@ class PC {
   std::vector<double> Efac, EfacT;
   std::vector<int> Epiv;
   bool E_chol = true;
+  bool E_dev = false;     // d_EL / d_ELT were factored on the device (block size E_nb): blocked sweeps in coarse_solve_local
+  int E_nb = 0;
+  bool factor_E_on_device(const std::vector<double>& sym);
   std::vector<double> h_yE;
   std::vector<double> h_Dscratch;   // partition of unity on the host, reused by the next set-up
   double cheb_lmax = 2.0, cheb_lmax1 = 2.0;

@@ -283,6 +283,14 @@ class GenEOPC:
         self.lib.PCGenEOGetLocalParams(self.h, t.ctypes.data_as(L.c_dbl_p), g.ctypes.data_as(L.c_dbl_p), n)
         return t[:n], g[:n]
 
+    def coarse_info(self):
+        """(dimE, factor_on_device, solve_kind, block) after the set-up (PCGenEOGetCoarseInfo): whether the blocked device
+        factorisation made the factor of E, and how E^-1 is applied -- 0 host round trip, 1 one-workgroup device sweeps,
+        2 blocked device sweeps with that block size."""
+        v = [C.c_int(0) for _ in range(4)]
+        self._chk(self.lib.PCGenEOGetCoarseInfo(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def local_dims(self):
         n = self.lib.PCGenEOGetLocalDims(self.h, None, 0)
         out = np.zeros(max(1, n), dtype=np.int32)

@@ -382,6 +382,23 @@ PetscErrorCode GeneoTestLobpcgUpdate(int nsub, const int* suboff, const double* 
  * Returns the primitive's own result (void: 0, bool: 0 / 1, recip_positive: its count), -1 on an error
  * (PCGenEOGetError(NULL)), -2 for an unknown name. */
 int GeneoTestPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
+
+/* ---- the coarse operator E on the device at any dimE (-geneo_coarse_device auto|never|always, -geneo_coarse_block nb) ----
+ * Where this PC factored E and how it applies E^-1, after the set-up.  factor_on_device: 1 when the blocked device
+ * factorisation made the factor, 0 for the host's (Cholesky or LU).  solve_kind: 0 download / host sweeps / upload,
+ * 1 the one-workgroup device sweeps (dimE <= 1024), 2 the blocked device sweeps.  block: their block size (0 unless 2). */
+PetscErrorCode PCGenEOGetCoarseInfo(PC pc, int* dimE, int* factor_on_device, int* solve_kind, int* block);
+/* Test hooks of the blocked kernels, HOST arrays (n x n row-major).  GeneoTestCoarseFactor: E = L L^T with block size nb;
+ * L lower with a zero strict upper part, LT its transpose, *status 0 or 1 + the index of the first pivot that was not
+ * positive.  GeneoTestCoarseSolve: y <- (L L^T)^-1 y, `reps` >= 1 times from the same y (timing).  Every device buffer of
+ * the hooks lies between canary pads and is read back: a write outside an array, a changed input or a HIP error is
+ * reported.  nb == 0 runs the host code the PC uses without these kernels (host Cholesky; download, host sweeps, upload).
+ * Returns 0 ok, -1 error (PCGenEOGetError(NULL)), -3 the backend has no such kernels.
+ * GeneoTestCoarseElapsed: milliseconds of the last factorisation and of one repetition of the last solve (device time
+ * between two events; wall time for nb == 0; -1 before the first call). */
+int GeneoTestCoarseFactor(int n, int nb, const double* E, double* L, double* LT, int* status);
+int GeneoTestCoarseSolve(int n, int nb, const double* L, const double* LT, double* y, int reps);
+int GeneoTestCoarseElapsed(double* factor_ms, double* solve_ms);
 /* cg_start and `iters` steps [spmv, seg_pap, cg_update, cg_direction] of the batched CG on the matrix of `h`
  * (suboff[nsub] rows) with one chunk list alive across the sequence; caller_precond != 0: the form with dinv == NULL in
  * cg_start / cg_update (z = dinv .* r by xmy, seg_partial(r, z, 1), cg_set_rz).  Device vectors; sc_out: host, nsub x 8. */
