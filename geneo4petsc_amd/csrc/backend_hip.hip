@@ -22,6 +22,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <map>
 #include <mutex>
 #include <unordered_map>
@@ -1776,20 +1777,9 @@ __global__ __launch_bounds__(256) void k_spmv_lds(const int* __restrict__ rowblk
 __device__ __forceinline__ int4 lp_base_of(const int* __restrict__ base, int s) {
   return base ? reinterpret_cast<const int4*>(base)[s] : int4{0, 0, 0x7fffffff, 0};
 }
-// Sliced kernel: one wave per 64-row slice, lane i owns row i.  Per k the wave issues one coalesced
-// 512-B val load, one 256-B col load and one x gather whose 64 addresses are the k-th neighbours of
-// 64 consecutive rows (contiguous for stencil-like matrices) -- no LDS round trip, no barrier.
-// UNR independent k-steps are in flight per lane; NT marks the once-read (col,val) stream
-// non-temporal so that it does not displace x from the XCD's L2.
-// COLT = unsigned short: the columns are read as 16-bit offsets from the slice's lowest column (cbase[s]; the index
-// arrays of the single-precision companion, shared) -- 10 bytes per entry instead of 12 with the FP64 values untouched.
-// Slices of KW <= 8 entries per row with every (col, val) load in front of the first gather and all gathers in flight
-// together -- two dependent latencies instead of up to eight -- and the products summed in the order of the 4-step loop of
-// k_spmv_sell<4, ..> below (KW / 4 rounds into four accumulators, the remainder into the first, then acc0 + acc1 + acc2 +
-// acc3): bit-identical to it.  (k_spmv_sell_p8 further down is the round-3 form of the same idea with another summation
-// order; the single-precision companion kernels have theirs in lp_row_sum_fixed.)
-// Where the fixed forms (here and lp_row_sum_fixed) take the columns c[u] of a row from: `at` runs inside the load loop,
-// next to the value load of the same entry; `finish` runs between the last value load and the first gather.
+// Sliced kernels (spmv_sell_slice below): a wave owns a 64-row slice, lane i owns row i.
+// Where the fixed forms (row_sum_fixed) take the columns c[u] of a row from: `at` runs inside the load loop, next to the
+// value load of the same entry; `finish` runs between the last value load and the first gather.
 // ColsStored: the stored column stream (COLT = int: sl_col; unsigned short: lp_col, offsets from the slice's bases cb).
 template <typename COLT, bool NT>
 struct ColsStored {
@@ -1834,20 +1824,105 @@ struct ColsOffset {
     }
   }
 };
-template <int KW, bool NT, typename SRC>
-__device__ __forceinline__ double spmv_row_sum_fixed(const SRC& src, const double* __restrict__ val, int64_t e0,
-                                                     const double* __restrict__ x) {
+// ------------------------------------------------------------------------------- the multigrid epilogues, once
+// The epilogues of backend.h (EPI_RES / ADD / JAC / POST / PRE) that ride on the output write of every single-vector and
+// block product below: the vector passes that used to follow the product (residual, correction, Jacobi update).
+// EpiReads: which of the row's operands an epilogue reads (each kernel loads them where it always did -- in front of its
+// matrix stream or behind its sum -- and only these).
+template <int EPI>
+struct EpiReads {
+  static constexpr bool b = EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE;
+  static constexpr bool z = EPI == EPI_ADD || EPI == EPI_POST;
+  static constexpr bool x = EPI == EPI_JAC;
+  // dinv: EPI_PRE needs it for its second output z = w dinv b alone (zout: where that goes, null when nobody wants it)
+  static __device__ __forceinline__ bool d(const double* zout) {
+    return EPI == EPI_JAC || EPI == EPI_POST || (EPI == EPI_PRE && zout);
+  }
+};
+// The y value of a row (a component of a row, in the block kernels) from its sum; EPI_PRE also gives the z value.
+template <int EPI>
+__device__ __forceinline__ double epi_apply(double sum, double e_b, double e_z, double e_d, double e_x, double w,
+                                            double& zout) {
+  if (EPI == EPI_NONE) {
+    return sum;
+  } else if (EPI == EPI_RES) {
+    return e_b - sum;
+  } else if (EPI == EPI_ADD) {
+    return e_z + sum;
+  } else if (EPI == EPI_JAC) {
+    return e_x + w * e_d * (e_b - sum);
+  } else if (EPI == EPI_POST) {
+    return w * e_d * (e_z + e_b) + sum;
+  } else {  // EPI_PRE (the product ran over x = b, columns scaled by dinv)
+    zout = w * e_d * e_b;
+    return e_b - w * sum;
+  }
+}
+// the single-vector kernels: the operands of row r, and the row's write
+struct EpiRow {
+  double b = 0.0, z = 0.0, d = 0.0, x = 0.0;
+};
+template <int EPI>
+__device__ __forceinline__ EpiRow epi_load_row(int64_t r, const double* __restrict__ b, const double* __restrict__ z,
+                                               const double* __restrict__ dinv, const double* __restrict__ x) {
+  EpiRow e;
+  if (EpiReads<EPI>::b) e.b = b[r];
+  if (EpiReads<EPI>::z) e.z = z[r];
+  if (EpiReads<EPI>::d(z)) e.d = dinv[r];
+  if (EpiReads<EPI>::x) e.x = x[r];
+  return e;
+}
+template <int EPI>
+__device__ __forceinline__ void epi_store_row(int64_t r, double sum, const EpiRow& e, double w, double* __restrict__ y,
+                                              double* __restrict__ z) {
+  double zv = 0.0;
+  const double yv = epi_apply<EPI>(sum, e.b, e.z, e.d, e.x, w, zv);
+  if (EPI == EPI_PRE && z) z[r] = zv;
+  y[r] = yv;
+}
+
+// ------------------------------------------------------------------------------- one traversal of a slice
+// What differs between the four sliced kernels besides their template arguments:
+//   pair_sum   how the four accumulators meet: (a0 + a1) + (a2 + a3), or ((a0 + a1) + a2) + a3 as the first FP64 kernels did
+//   narrow     slices of 1 .. 8 entries per row take the two-latency form (row_sum_fixed)
+//   p16        slices of 9 .. 16 entries per row take the predicated form (lp_row_sum_p16; float values)
+//   epi_early  the epilogue's operands are loaded in front of the matrix stream, not behind the sum
+template <bool PAIR_SUM, bool NARROW, bool P16, bool EPI_EARLY>
+struct SlicePolicy {
+  static constexpr bool pair_sum = PAIR_SUM, narrow = NARROW, p16 = P16, epi_early = EPI_EARLY;
+  static_assert(NARROW || !P16, "the predicated form continues the narrow forms");
+  static __device__ __forceinline__ double sum4(const double (&acc)[4]) {
+    return PAIR_SUM ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : ((acc[0] + acc[1]) + acc[2]) + acc[3];
+  }
+};
+typedef SlicePolicy<false, true, false, true> SliceSell;    // k_spmv_sell
+typedef SlicePolicy<false, false, false, true> SliceEpi;    // k_spmv_sell_epi
+typedef SlicePolicy<true, false, false, false> SliceWide;   // k_spmv_sell_wide
+typedef SlicePolicy<true, true, true, true> SliceLp;        // k_spmv_sell_lp
+
+// A slice of KW <= 8 entries per row in TWO dependent memory latencies: every (col, val) pair of the slice is requested
+// before the first x gather and all gathers are in flight together.  The 4-step loop sends a 7-wide slice -- every
+// fine-level operator of the benchmark -- through one round of four and three one-at-a-time tail steps: eight dependent
+// latencies per wave, and a wave holds one 64-row slice, so its run time IS that chain (0.46-0.54 of the
+// HBM peak while the FP64 SpMV on the same pattern reaches 0.72).  The products are summed exactly as that loop sums them
+// (KW / 4 rounds into four accumulators, the remainder into the first, then the policy's final sum): results are
+// bit-identical to it.
+// VT: the stored values (double; float in the companion: widened on load, FP64 arithmetic).  SRC: where the columns come from
+// (ColsStored: the stored stream; ColsOffset: an offset-coded slice).  EPI_PRE with cs: the columns of the product are scaled.
+template <int KW, typename VT, int EPI, bool NT, typename POL, typename SRC>
+__device__ __forceinline__ double row_sum_fixed(const SRC& src, const VT* __restrict__ val, int64_t e0,
+                                                const double* __restrict__ xin, const double* __restrict__ cs) {
   int c[KW];
   double v[KW];
 #pragma unroll
   for (int u = 0; u < KW; ++u) {
     c[u] = src.at(u, e0);
-    v[u] = NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u];
+    v[u] = (double)(NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u]);
   }
   src.template finish<KW>(c);
   double xv[KW];
 #pragma unroll
-  for (int u = 0; u < KW; ++u) xv[u] = x[c[u]];
+  for (int u = 0; u < KW; ++u) xv[u] = (EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]];
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   constexpr int NG = KW / 4;
 #pragma unroll
@@ -1856,205 +1931,196 @@ __device__ __forceinline__ double spmv_row_sum_fixed(const SRC& src, const doubl
     for (int u = 0; u < 4; ++u) acc[u] += v[4 * g + u] * xv[4 * g + u];
 #pragma unroll
   for (int k = 4 * NG; k < KW; ++k) acc[0] += v[k] * xv[k];
-  return ((acc[0] + acc[1]) + acc[2]) + acc[3];
+  return POL::sum4(acc);
 }
 // the fixed form of a slice of wd = 1 .. 8 entries per row (wd is wave-uniform)
-template <bool NT, typename SRC>
-__device__ __forceinline__ double spmv_row_sum_narrow(int wd, const SRC& src, const double* __restrict__ val, int64_t e0,
-                                                      const double* __restrict__ x) {
+template <typename VT, int EPI, bool NT, typename POL, typename SRC>
+__device__ __forceinline__ double row_sum_narrow(int wd, const SRC& src, const VT* __restrict__ val, int64_t e0,
+                                                 const double* __restrict__ xin, const double* __restrict__ cs) {
   switch (wd) {
-    case 1: return spmv_row_sum_fixed<1, NT>(src, val, e0, x);
-    case 2: return spmv_row_sum_fixed<2, NT>(src, val, e0, x);
-    case 3: return spmv_row_sum_fixed<3, NT>(src, val, e0, x);
-    case 4: return spmv_row_sum_fixed<4, NT>(src, val, e0, x);
-    case 5: return spmv_row_sum_fixed<5, NT>(src, val, e0, x);
-    case 6: return spmv_row_sum_fixed<6, NT>(src, val, e0, x);
-    case 7: return spmv_row_sum_fixed<7, NT>(src, val, e0, x);
-    default: return spmv_row_sum_fixed<8, NT>(src, val, e0, x);
+    case 1: return row_sum_fixed<1, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 2: return row_sum_fixed<2, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 3: return row_sum_fixed<3, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 4: return row_sum_fixed<4, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 5: return row_sum_fixed<5, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 6: return row_sum_fixed<6, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    case 7: return row_sum_fixed<7, VT, EPI, NT, POL>(src, val, e0, xin, cs);
+    default: return row_sum_fixed<8, VT, EPI, NT, POL>(src, val, e0, xin, cs);
   }
 }
-// OFFS: the matrix carries offset-coded columns (omask / orec = Csr::off_mask / off_rec): a coded slice takes its columns
-// from them (ColsOffset) and reads no column stream; a slice that is not coded (wave-uniform test of its record) runs the
-// code below as it stands.
-template <int UNR, bool NT, typename COLT = int, bool OFFS = false>
+// The same for slices of 9 .. 16 entries per row (the post-smoothing matrices M = P - w D^-1 A P of the V-cycle: 12 wide on
+// the 7-point problem, three rounds of the 4-step loop = six dependent latencies): sixteen predicated steps (wd is
+// wave-uniform: scalar branches, lanes past the width load nothing), all loads, then all gathers, then the products in the
+// loop's order -- entry u < 4 (wd / 4) goes to accumulator u mod 4, the remainder to the first, in increasing u.
+// (The same sequence for the workgroup-per-slice kernel -- each of its four waves owning every fourth entry of a row -- was
+//  measured on one box, three runs each at 6.5 M rows: companion passes 82 us with the wave-per-slice forms alone, 92 us with
+//  both, 92 us with neither (profiles/r04_lp_two_latency_ab.log): it costs what the narrow forms gain, and is not built.)
+template <int EPI, typename COLT, bool NT>
+__device__ __forceinline__ double lp_row_sum_p16(const COLT* __restrict__ col, const float* __restrict__ val, int64_t e0,
+                                                 int wd, const int4 cb, const double* __restrict__ xin,
+                                                 const double* __restrict__ cs) {
+  int c[16];
+  double v[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    c[u] = cb.x;
+    v[u] = 0.0;
+    if (u < wd) {
+      c[u] = (u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e0 + 64 * u) : col[e0 + 64 * u]);
+      v[u] = (double)(NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u]);
+    }
+  }
+  double xv[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    xv[u] = 0.0;
+    if (u < wd) xv[u] = (EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]];
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const int ng4 = (wd >> 2) << 2;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    if (u < ng4) acc[u & 3] += v[u] * xv[u];
+    else if (u < wd) acc[0] += v[u] * xv[u];
+  }
+  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+// The body of k_spmv_sell, k_spmv_sell_epi, k_spmv_sell_wide and k_spmv_sell_lp: y = epilogue(A x) on the 64-row slices,
+// four k-steps in flight per lane, then a one-at-a-time tail; summation order fixed.
+// WPS = 1: one wave per slice (four slices per workgroup).  WPS = 4: ONE WORKGROUP owns a slice (wide slices: coarse Galerkin
+// operators, restrictions -- 30-60 entries per row on a few thousand slices; with one wave per slice the wave's own chain of
+// dependent (col, val) -> x loads is the whole run time and most of the chip idles): wave w takes the entries k = w, w + 4,
+// ... (4 of them in flight per lane, 16 per row across the workgroup), the four partial sums meet in LDS and wave 0 runs
+// the epilogue.
+// COLT = unsigned short: the columns are 16-bit offsets from the slice's bases (base: {b0, b1, ks, -} per slice, k_lp_base;
+// null: 32-bit columns as they stand).  NT: the once-read (col, val) stream of a LARGE matrix is marked non-temporal (the
+// vectors, not the matrix, are what the caches should keep); a hint only -- same loads, same arithmetic.
+// OFFS (WPS = 1 only): the matrix carries offset-coded columns (omask / orec = Csr::off_mask / off_rec): a coded slice takes
+// its columns from them (ColsOffset) and reads no column stream; a slice that is not coded (wave-uniform test of its record)
+// runs the stored columns.
+template <typename VT, typename COLT, int EPI, int WPS, bool NT, bool OFFS, typename POL>
+__device__ __forceinline__ void spmv_sell_slice(const int64_t* __restrict__ sl_ptr, int nslice, int n,
+                                                const COLT* __restrict__ col, const VT* __restrict__ val,
+                                                const int* __restrict__ base, const double* __restrict__ x,
+                                                double* __restrict__ y, const double* __restrict__ b,
+                                                double* __restrict__ z, const double* __restrict__ dinv, double w,
+                                                const double* __restrict__ cs /* EPI_PRE: column scaling, null when the values carry it */,
+                                                const unsigned char* __restrict__ omask, const int* __restrict__ orec) {
+  static_assert(WPS == 1 || (WPS == 4 && !OFFS), "a coded slice belongs to one wave");
+  constexpr bool FIXED = POL::narrow && WPS == 1;   // the fixed forms are wave-per-slice
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  int s;
+  if (WPS == 1) {
+    const int nwb = (nslice + 3) >> 2;            // workgroups (4 slices each)
+    const int t = xcd_remap(blockIdx.x, nwb);
+    s = 4 * t + wv;
+    if (t >= nwb || s >= nslice) return;
+  } else {
+    s = xcd_remap(blockIdx.x, nslice);
+    if (s >= nslice) return;
+  }
+  // OFFS: the slice index is made visibly wave-uniform, so that the slice's pointers, record and bases come through scalar
+  // loads issued together, and the width below selects its case by scalar branches
+  const int su = OFFS ? __builtin_amdgcn_readfirstlane(s) : s;
+  const int64_t a = sl_ptr[su], e1 = sl_ptr[su + 1];
+  const int4 cb = lp_base_of(base, su);  // {b0, b1, ks}: entries k < ks count from b0, the others from b1
+  int4 o0 = int4{OFF_NONE, 0, 0, 0}, o1 = int4{0, 0, 0, 0};
+  int nofix = 0;
+  if (OFFS) {                            // requested with the pointers and the bases: one wait for all of them
+    const int4* rec = reinterpret_cast<const int4*>(orec) + 2 * (int64_t)su;
+    o0 = rec[0];
+    o1 = rec[1];
+    nofix = g_lp_no_fixed;
+  }
+  const double* __restrict__ xin = (EPI == EPI_PRE) ? b : x;
+  // The epilogue's own operands do not depend on the product: with epi_early their loads are issued HERE, in front of the
+  // matrix stream, instead of after the last gather has come back (one dependent memory round trip less per wave; a wave
+  // holds one 64-row slice, so its run time is a chain of round trips, not bandwidth).  Same arithmetic, same results.
+  const int r = 64 * s + l;
+  unsigned char om = 0;
+  int oov = 0;
+  if (OFFS) {                             // the presence mask and the offsets by lane: first in the queue, the decode waits for them alone
+    om = omask[r];
+    oov = orec[8 * (int64_t)su + (l & 7)];
+  }
+  EpiRow ep;
+  if (POL::epi_early && r < n && (WPS == 1 || wv == 0)) ep = epi_load_row<EPI>(r, b, z, dinv, x);
+  constexpr int STEP = 64 * WPS;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  int64_t e = a + (WPS == 1 ? 0 : 64 * wv) + l;
+  int k = (WPS == 1 ? 0 : wv);            // entry index of e within its row
+  // narrow slice: the two-latency forms (same sums, same order)
+  const int wd = (int)((e1 - a) >> 6);    // entries per row of this slice (wave-uniform)
+  double fixed_sum = 0.0;
+  bool fixed = false;
+  if constexpr (FIXED) fixed = wd >= 1 && wd <= (POL::p16 ? 16 : 8) && !(OFFS ? nofix : g_lp_no_fixed);
+  if constexpr (FIXED) {
+    if (OFFS && fixed && o0.x != OFF_NONE) {   // coded slices are 1 .. 8 entries wide
+      fixed_sum = row_sum_narrow<VT, EPI, NT, POL>(wd, ColsOffset{o0, o1, om, oov, r, r < n ? r : n - 1}, val, e, xin, cs);
+      e = e1;
+    } else if (POL::p16 && fixed && wd > 8) {
+      if constexpr (POL::p16) fixed_sum = lp_row_sum_p16<EPI, COLT, NT>(col, val, e, wd, cb, xin, cs);
+      e = e1;
+    } else if (fixed) {
+      fixed_sum = row_sum_narrow<VT, EPI, NT, POL>(wd, ColsStored<COLT, NT>{col, cb}, val, e, xin, cs);
+      e = e1;                               // nothing left for the general loops below
+    }
+  }
+  for (; e + STEP * 3 < e1; e += STEP * 4, k += WPS * 4) {
+    int c[4];
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      c[u] = (k + WPS * u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e + STEP * u) : col[e + STEP * u]);
+      v[u] = (double)(NT ? __builtin_nontemporal_load(val + e + STEP * u) : val[e + STEP * u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] += v[u] * ((EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]]);
+  }
+  for (; e < e1; e += STEP, k += WPS) {
+    const int c0 = (k < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e) : col[e]);
+    const double v0 = (double)(NT ? __builtin_nontemporal_load(val + e) : val[e]);
+    acc[0] += v0 * ((EPI == EPI_PRE && cs) ? xin[c0] * cs[c0] : xin[c0]);
+  }
+  double sum = fixed ? fixed_sum : POL::sum4(acc);
+  if (WPS == 4) {
+    __shared__ double part[3][64];
+    if (wv > 0) part[wv - 1][l] = sum;
+    __syncthreads();
+    if (wv > 0) return;
+    sum = (sum + part[0][l]) + (part[1][l] + part[2][l]);
+  }
+  if (r >= n) return;
+  if (!POL::epi_early) ep = epi_load_row<EPI>(r, b, z, dinv, x);
+  epi_store_row<EPI>(r, sum, ep, w, y, z);
+}
+
+// FP64 values, one wave per slice, no epilogue.  Per k the wave issues one coalesced 512-B val load, one 256-B col load and
+// one x gather whose 64 addresses are the k-th neighbours of 64 consecutive rows (contiguous for stencil-like matrices) --
+// no LDS round trip, no barrier.  COLT = unsigned short: the index arrays of the single-precision companion, shared -- 10
+// bytes per entry instead of 12 with the FP64 values untouched.
+template <bool NT, typename COLT = int, bool OFFS = false>
 __global__ __launch_bounds__(256) void k_spmv_sell(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                    const COLT* __restrict__ col, const double* __restrict__ val,
                                                    const double* __restrict__ x, double* __restrict__ y,
                                                    const int* __restrict__ cbase = nullptr,
                                                    const unsigned char* __restrict__ omask = nullptr,
                                                    const int* __restrict__ orec = nullptr) {
-  const int nwb = (nslice + 3) >> 2;            // workgroups (4 slices each)
-  const int t = xcd_remap(blockIdx.x, nwb);
-  const int s = 4 * t + (threadIdx.x >> 6);
-  if (t >= nwb || s >= nslice) return;
-  const int l = threadIdx.x & 63;
-  // OFFS: the slice index is made visibly wave-uniform, so that the slice's pointers, record and bases come through scalar
-  // loads issued together, and the width below selects its case by scalar branches
-  const int su = OFFS ? __builtin_amdgcn_readfirstlane(s) : s;
-  const int64_t a = sl_ptr[su], b = sl_ptr[su + 1];
-  if (OFFS && UNR == 4) {
-    // everything the decision needs is requested before anything is tested: one wait, not one per operand
-    const int rr = 64 * s + l;
-    const unsigned char m = omask[rr];          // in flight with the record and, below, the values
-    const int ov = orec[8 * (int64_t)su + (l & 7)];
-    const int4* rec = reinterpret_cast<const int4*>(orec) + 2 * (int64_t)su;
-    const int4 o0 = rec[0], o1 = rec[1];
-    const int nofix = g_lp_no_fixed;
-    if ((o0.x != OFF_NONE) & (nofix == 0)) {    // coded slices are 1 .. 8 entries wide
-      const ColsOffset src{o0, o1, m, ov, rr, rr < n ? rr : n - 1};
-      const double fs = spmv_row_sum_narrow<NT>((int)((b - a) >> 6), src, val, a + l, x);
-      if (rr < n) y[rr] = fs;
-      return;
-    }
-  }
-  const int4 cb = lp_base_of(cbase, su);      // {b0, b1, ks}: entries k < ks count from b0, the others from b1
-  if (UNR == 4 && !g_lp_no_fixed) {           // narrow slice: the two-latency form (same sums, same order)
-    const int wd = (int)((b - a) >> 6);
-    if (wd >= 1 && wd <= 8) {
-      const double fs = spmv_row_sum_narrow<NT>(wd, ColsStored<COLT, NT>{col, cb}, val, a + l, x);
-      const int rr = 64 * s + l;
-      if (rr < n) y[rr] = fs;
-      return;
-    }
-  }
-  double acc[UNR];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) acc[u] = 0.0;
-  int64_t e = a + l;
-  int k = 0;
-  for (; e + 64 * (UNR - 1) < b; e += 64 * UNR, k += UNR) {
-    int c[UNR];
-    double v[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      c[u] = (k + u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e + 64 * u) : col[e + 64 * u]);
-      v[u] = NT ? __builtin_nontemporal_load(val + e + 64 * u) : val[e + 64 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) acc[u] += v[u] * x[c[u]];
-  }
-  for (; e < b; e += 64, ++k) {
-    const int c0 = (k < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e) : col[e]);
-    const double v0 = NT ? __builtin_nontemporal_load(val + e) : val[e];
-    acc[0] += v0 * x[c0];
-  }
-  double sum = acc[0];
-#pragma unroll
-  for (int u = 1; u < UNR; ++u) sum += acc[u];
-  const int r = 64 * s + l;
-  if (r < n) y[r] = sum;
+  spmv_sell_slice<double, COLT, EPI_NONE, 1, NT, OFFS, SliceSell>(sl_ptr, nslice, n, col, val, cbase, x, y, nullptr, nullptr,
+                                                                  nullptr, 0.0, nullptr, omask, orec);
 }
-
-// The same traversal with EIGHT predicated k-steps per round: a slice of a 7-point matrix is 7 entries wide, and with
-// the 4-step loop above its last three entries go through the one-at-a-time tail -- three more dependent
-// (col -> x) latency pairs per wave.  Here every (col, val) pair of the slice is requested before the first x gather
-// and all gathers are in flight together: two dependent latencies per slice.  Lanes past the slice's width load nothing
-// (predicated), so no extra traffic.
-template <bool NT, typename COLT = int>
-__global__ __launch_bounds__(256) void k_spmv_sell_p8(const int64_t* __restrict__ sl_ptr, int nslice, int n,
-                                                      const COLT* __restrict__ col, const double* __restrict__ val,
-                                                      const double* __restrict__ x, double* __restrict__ y,
-                                                      const int* __restrict__ cbase = nullptr) {
-  const int nwb = (nslice + 3) >> 2;
-  const int t = xcd_remap(blockIdx.x, nwb);
-  const int s = 4 * t + (threadIdx.x >> 6);
-  if (t >= nwb || s >= nslice) return;
-  const int l = threadIdx.x & 63;
-  const int64_t a = sl_ptr[s], b = sl_ptr[s + 1];
-  const int4 cb = lp_base_of(cbase, s);
-  double acc0 = 0.0, acc1 = 0.0;
-  int k = 0;
-  for (int64_t e = a + l; e < b; e += 64 * 8, k += 8) {
-    int c[8];
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const bool ok = e + 64 * u < b;
-      c[u] = cb.x;
-      v[u] = 0.0;
-      if (ok) {
-        c[u] = (k + u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e + 64 * u) : col[e + 64 * u]);
-        v[u] = NT ? __builtin_nontemporal_load(val + e + 64 * u) : val[e + 64 * u];
-      }
-    }
-    double xv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) xv[u] = x[c[u]];
-#pragma unroll
-    for (int u = 0; u < 8; u += 2) {
-      acc0 += v[u] * xv[u];
-      acc1 += v[u + 1] * xv[u + 1];
-    }
-  }
-  const int r = 64 * s + l;
-  if (r < n) y[r] = acc0 + acc1;
-}
-// Same traversal with the multigrid epilogues of backend.h fused in (EPI_RES / ADD / JAC / PRE): the vector
-// passes that used to follow the SpMV (residual, correction, Jacobi update) ride on its output write.
+// The same with the multigrid epilogues fused in, over the 32-bit columns and the 4-step loop alone.
 template <bool NT, int EPI>
 __global__ __launch_bounds__(256) void k_spmv_sell_epi(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                        const int* __restrict__ col, const double* __restrict__ val,
                                                        const double* __restrict__ x, double* __restrict__ y,
                                                        const double* __restrict__ b, double* __restrict__ z,
                                                        const double* __restrict__ dinv, double w,
-                                                       const double* __restrict__ cs /* EPI_PRE: column scaling, null when the values carry it */) {
-  constexpr int UNR = 4;
-  const int nwb = (nslice + 3) >> 2;
-  const int t = xcd_remap(blockIdx.x, nwb);
-  const int s = 4 * t + (threadIdx.x >> 6);
-  if (t >= nwb || s >= nslice) return;
-  const int l = threadIdx.x & 63;
-  const int64_t a = sl_ptr[s], e1 = sl_ptr[s + 1];
-  // the epilogue's own operands, loaded in front of the matrix stream (see k_spmv_sell_lp)
-  const int r = 64 * s + l;
-  double e_b = 0.0, e_z = 0.0, e_d = 0.0, e_x = 0.0;
-  if (r < n) {
-    if (EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE) e_b = b[r];
-    if (EPI == EPI_ADD || EPI == EPI_POST) e_z = z[r];
-    if (EPI == EPI_JAC || EPI == EPI_POST || (EPI == EPI_PRE && z)) e_d = dinv[r];
-    if (EPI == EPI_JAC) e_x = x[r];
-  }
-  double acc[UNR];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) acc[u] = 0.0;
-  int64_t e = a + l;
-  for (; e + 64 * (UNR - 1) < e1; e += 64 * UNR) {
-    int c[UNR];
-    double v[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      c[u] = NT ? __builtin_nontemporal_load(col + e + 64 * u) : col[e + 64 * u];
-      v[u] = NT ? __builtin_nontemporal_load(val + e + 64 * u) : val[e + 64 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) acc[u] += v[u] * (EPI == EPI_PRE ? (cs ? b[c[u]] * cs[c[u]] : b[c[u]]) : x[c[u]]);
-  }
-  for (; e < e1; e += 64) {
-    const int c0 = NT ? __builtin_nontemporal_load(col + e) : col[e];
-    const double v0 = NT ? __builtin_nontemporal_load(val + e) : val[e];
-    acc[0] += v0 * (EPI == EPI_PRE ? (cs ? b[c0] * cs[c0] : b[c0]) : x[c0]);
-  }
-  double sum = acc[0];
-#pragma unroll
-  for (int u = 1; u < UNR; ++u) sum += acc[u];
-  if (r >= n) return;
-  if (EPI == EPI_RES) {
-    y[r] = e_b - sum;
-  } else if (EPI == EPI_ADD) {
-    y[r] = e_z + sum;
-  } else if (EPI == EPI_JAC) {
-    y[r] = e_x + w * e_d * (e_b - sum);
-  } else if (EPI == EPI_POST) {
-    y[r] = w * e_d * (e_z + e_b) + sum;
-  } else {  // EPI_PRE
-    if (z) z[r] = w * e_d * e_b;
-    y[r] = e_b - w * sum;
-  }
+                                                       const double* __restrict__ cs) {
+  spmv_sell_slice<double, int, EPI, 1, NT, false, SliceEpi>(sl_ptr, nslice, n, col, val, nullptr, x, y, b, z, dinv, w, cs,
+                                                            nullptr, nullptr);
 }
-// Wide slices (coarse Galerkin operators, restrictions: 30-60 entries per row on a few thousand slices): with one wave
-// per slice the wave's own chain of dependent (col,val) -> x loads is the whole run time and most of the chip idles.
-// Here ONE WORKGROUP owns a slice: wave w takes the entries k = w, w + 4, ... (4 of them in flight per lane, 16 per row
-// across the workgroup), the four partial sums meet in LDS and wave 0 runs the epilogue.  Summation order is fixed.
+// Wide slices: one workgroup per slice, cached stream, the epilogue's operands loaded behind the sum.
 template <int EPI>
 __global__ __launch_bounds__(256) void k_spmv_sell_wide(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                         const int* __restrict__ col, const double* __restrict__ val,
@@ -2062,54 +2128,8 @@ __global__ __launch_bounds__(256) void k_spmv_sell_wide(const int64_t* __restric
                                                         const double* __restrict__ b, double* __restrict__ z,
                                                         const double* __restrict__ dinv, double w,
                                                         const double* __restrict__ cs) {
-  constexpr int UNR = 4;
-  __shared__ double part[3][64];
-  const int s = xcd_remap(blockIdx.x, nslice);
-  if (s >= nslice) return;
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int64_t a = sl_ptr[s], e1 = sl_ptr[s + 1];
-  const double* __restrict__ xin = (EPI == EPI_PRE) ? b : x;
-  double acc[UNR];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) acc[u] = 0.0;
-  int64_t e = a + 64 * wv + l;
-  for (; e + 256 * (UNR - 1) < e1; e += 256 * UNR) {
-    int c[UNR];
-    double v[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      c[u] = col[e + 256 * u];
-      v[u] = val[e + 256 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) acc[u] += v[u] * ((EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]]);
-  }
-  for (; e < e1; e += 256) {
-    const int c0 = col[e];
-    acc[0] += val[e] * ((EPI == EPI_PRE && cs) ? xin[c0] * cs[c0] : xin[c0]);
-  }
-  double sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  if (wv > 0) part[wv - 1][l] = sum;
-  __syncthreads();
-  if (wv > 0) return;
-  sum = (sum + part[0][l]) + (part[1][l] + part[2][l]);
-  const int r = 64 * s + l;
-  if (r >= n) return;
-  if (EPI == EPI_NONE) {
-    y[r] = sum;
-  } else if (EPI == EPI_RES) {
-    y[r] = b[r] - sum;
-  } else if (EPI == EPI_ADD) {
-    y[r] = z[r] + sum;
-  } else if (EPI == EPI_JAC) {
-    y[r] = x[r] + w * dinv[r] * (b[r] - sum);
-  } else if (EPI == EPI_POST) {
-    y[r] = w * dinv[r] * (z[r] + b[r]) + sum;
-  } else {  // EPI_PRE
-    const double bb = b[r];
-    if (z) z[r] = w * dinv[r] * bb;
-    y[r] = bb - w * sum;
-  }
+  spmv_sell_slice<double, int, EPI, 4, false, false, SliceWide>(sl_ptr, nslice, n, col, val, nullptr, x, y, b, z, dinv, w, cs,
+                                                                nullptr, nullptr);
 }
 // Average slice width from which a workgroup (not a wave) owns a slice; 0 = never.  Single vectors: 16 (measured on the
 // 126^3 hierarchy: the 12-wide post-smoothing matrix P - w D^-1 A P runs 20 % faster wave-per-slice).  Blocks: 9 -- as
@@ -2485,96 +2505,9 @@ bool csr_make_lp(Csr& a, const Csr* index_owner) {
                      (const int4*)a.lp_base, (index_owner || !a.lp_col) ? (unsigned short*)nullptr : a.lp_col, a.lp_val);
   return true;
 }
-// A slice of KW <= 8 entries per row in TWO dependent memory latencies: every (col, val) pair of the slice is requested
-// before the first x gather and all gathers are in flight together (what k_spmv_sell_p8 does for the FP64 SpMV).  The
-// 4-step loop of k_spmv_sell_lp sends a 7-wide slice -- every fine-level operator of the benchmark -- through one round of
-// four and three one-at-a-time tail steps: eight dependent latencies per wave, and a wave holds one 64-row slice, so its
-// run time IS that chain (0.46-0.54 of the HBM peak while the FP64 SpMV on the same pattern reaches
-// 0.72).  The products are summed exactly as that loop sums them (KW / 4 rounds into four accumulators, the remainder
-// into the first): results are bit-identical.
-// SRC: where the columns come from (ColsStored: the stored stream; ColsOffset: an offset-coded slice), as in
-// spmv_row_sum_fixed.
-template <int KW, int EPI, bool NT, typename SRC>
-__device__ __forceinline__ double lp_row_sum_fixed(const SRC& src, const float* __restrict__ val, int64_t e0,
-                                                   const double* __restrict__ xin, const double* __restrict__ cs) {
-  int c[KW];
-  double v[KW];
-#pragma unroll
-  for (int u = 0; u < KW; ++u) {
-    c[u] = src.at(u, e0);
-    v[u] = (double)(NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u]);
-  }
-  src.template finish<KW>(c);
-  double xv[KW];
-#pragma unroll
-  for (int u = 0; u < KW; ++u) xv[u] = (EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]];
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  constexpr int NG = KW / 4;
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] += v[4 * g + u] * xv[4 * g + u];
-#pragma unroll
-  for (int k = 4 * NG; k < KW; ++k) acc[0] += v[k] * xv[k];
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-// The same for slices of 9 .. 16 entries per row (the post-smoothing matrices M = P - w D^-1 A P of the V-cycle: 12 wide on
-// the 7-point problem, three rounds of the 4-step loop = six dependent latencies): sixteen predicated steps (wd is
-// wave-uniform: scalar branches, lanes past the width load nothing), all loads, then all gathers, then the products in the
-// loop's order -- entry u < 4 (wd / 4) goes to accumulator u mod 4, the remainder to the first, in increasing u.
-// (The same sequence for the workgroup-per-slice kernel -- each of its four waves owning every fourth entry of a row -- was
-//  measured on one box, three runs each at 6.5 M rows: companion passes 82 us with the wave-per-slice forms alone, 92 us with
-//  both, 92 us with neither (profiles/r04_lp_two_latency_ab.log): it costs what the narrow forms gain, and is not built.)
-template <int EPI, typename COLT, bool NT>
-__device__ __forceinline__ double lp_row_sum_p16(const COLT* __restrict__ col, const float* __restrict__ val, int64_t e0,
-                                                 int wd, const int4 cb, const double* __restrict__ xin,
-                                                 const double* __restrict__ cs) {
-  int c[16];
-  double v[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    c[u] = cb.x;
-    v[u] = 0.0;
-    if (u < wd) {
-      c[u] = (u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e0 + 64 * u) : col[e0 + 64 * u]);
-      v[u] = (double)(NT ? __builtin_nontemporal_load(val + e0 + 64 * u) : val[e0 + 64 * u]);
-    }
-  }
-  double xv[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    xv[u] = 0.0;
-    if (u < wd) xv[u] = (EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]];
-  }
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  const int ng4 = (wd >> 2) << 2;
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    if (u < ng4) acc[u & 3] += v[u] * xv[u];
-    else if (u < wd) acc[0] += v[u] * xv[u];
-  }
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-template <int EPI, bool NT, typename SRC>
-__device__ __forceinline__ double lp_row_sum_narrow(int wd, const SRC& src, const float* __restrict__ val, int64_t e0,
-                                                    const double* __restrict__ xin, const double* __restrict__ cs) {
-  switch (wd) {
-    case 1: return lp_row_sum_fixed<1, EPI, NT>(src, val, e0, xin, cs);
-    case 2: return lp_row_sum_fixed<2, EPI, NT>(src, val, e0, xin, cs);
-    case 3: return lp_row_sum_fixed<3, EPI, NT>(src, val, e0, xin, cs);
-    case 4: return lp_row_sum_fixed<4, EPI, NT>(src, val, e0, xin, cs);
-    case 5: return lp_row_sum_fixed<5, EPI, NT>(src, val, e0, xin, cs);
-    case 6: return lp_row_sum_fixed<6, EPI, NT>(src, val, e0, xin, cs);
-    case 7: return lp_row_sum_fixed<7, EPI, NT>(src, val, e0, xin, cs);
-    default: return lp_row_sum_fixed<8, EPI, NT>(src, val, e0, xin, cs);
-  }
-}
-// WPS = 1: one wave per slice (four slices per workgroup), WPS = 4: one workgroup per slice (wide slices), as the FP64
-// kernels k_spmv_sell_epi / k_spmv_sell_wide above; summation order fixed.
-// NT: the once-read (col, val) stream of a LARGE companion is marked non-temporal, as in k_spmv_sell (the vectors of the
-// cycle, not the matrix, are what the caches should keep); a hint only -- same loads, same arithmetic.
-// OFFS (WPS = 1 only): the matrix carries offset-coded columns (omask / orec, see k_spmv_sell): coded slices read no column
-// stream, the others run today's code.
+// The passes over the single-precision companion (float values, 16-bit columns where the slices' spans allow them): the
+// wave-per-slice form with the two-latency forms for slices of up to 16 entries per row, and the workgroup-per-slice form
+// for wide slices (WPS = 4), every epilogue; FP64 arithmetic and vectors, summation order fixed.
 template <int EPI, int WPS, typename COLT, bool NT, bool OFFS = false>
 __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict__ sl_ptr, int nslice, int n,
                                                       const COLT* __restrict__ col, const float* __restrict__ val,
@@ -2584,108 +2517,29 @@ __global__ __launch_bounds__(256) void k_spmv_sell_lp(const int64_t* __restrict_
                                                       const double* __restrict__ cs,
                                                       const unsigned char* __restrict__ omask = nullptr,
                                                       const int* __restrict__ orec = nullptr) {
-  constexpr int UNR = 4;
-  __shared__ double part[3][64];
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  int s;
-  if (WPS == 1) {
-    const int nwb = (nslice + 3) >> 2;
-    const int t = xcd_remap(blockIdx.x, nwb);
-    s = 4 * t + wv;
-    if (t >= nwb || s >= nslice) return;
-  } else {
-    s = xcd_remap(blockIdx.x, nslice);
-    if (s >= nslice) return;
-  }
-  // OFFS: the slice index made visibly wave-uniform -- scalar loads of the slice's pointers, record and bases (see k_spmv_sell)
-  const int su = (OFFS && WPS == 1) ? __builtin_amdgcn_readfirstlane(s) : s;
-  const int64_t a = sl_ptr[su], e1 = sl_ptr[su + 1];
-  const int4 cb = lp_base_of(base, su);  // 16-bit columns are offsets from the slice's bases (k_lp_base)
-  int4 o0 = int4{OFF_NONE, 0, 0, 0}, o1 = int4{0, 0, 0, 0};
-  int nofix = 0;
-  if (OFFS && WPS == 1) {                // requested with the pointers and the bases: one wait for all of them
-    const int4* rec = reinterpret_cast<const int4*>(orec) + 2 * (int64_t)su;
-    o0 = rec[0];
-    o1 = rec[1];
-    nofix = g_lp_no_fixed;
-  }
-  const double* __restrict__ xin = (EPI == EPI_PRE) ? b : x;
-  // The epilogue's own operands do not depend on the product: their loads are issued HERE, in front of the matrix stream,
-  // instead of after the last gather has come back (one dependent memory round trip less per wave; a wave holds one
-  // 64-row slice, so its run time is a chain of round trips, not bandwidth).  Same arithmetic, same results.
-  const int r = 64 * s + l;
-  const bool rok = r < n && (WPS == 1 || wv == 0);
-  double e_b = 0.0, e_z = 0.0, e_d = 0.0, e_x = 0.0;
-  unsigned char om = 0;
-  int oov = 0;
-  if (OFFS && WPS == 1) {                 // the presence mask and the offsets by lane: first in the queue, the decode waits for them alone
-    om = omask[r];
-    oov = orec[8 * (int64_t)su + (l & 7)];
-  }
-  if (rok) {
-    if (EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE) e_b = b[r];
-    if (EPI == EPI_ADD || EPI == EPI_POST) e_z = z[r];
-    if (EPI == EPI_JAC || EPI == EPI_POST || (EPI == EPI_PRE && z)) e_d = dinv[r];
-    if (EPI == EPI_JAC) e_x = x[r];
-  }
-  constexpr int STEP = 64 * WPS;
-  double acc[UNR];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) acc[u] = 0.0;
-  int64_t e = a + (WPS == 1 ? 0 : 64 * wv) + l;
-  int k = (WPS == 1 ? 0 : wv);            // entry index of e within its row
-  const int wd = (int)((e1 - a) >> 6);    // entries per row of this slice (wave-uniform)
-  double fixed_sum = 0.0;
-  const bool fixed = (WPS == 1 && wd >= 1 && wd <= 16 && !((OFFS && WPS == 1) ? nofix : g_lp_no_fixed));
-  const bool coded = OFFS && fixed && o0.x != OFF_NONE;   // coded slices are 1 .. 8 entries wide
-  if (coded) {
-    fixed_sum = lp_row_sum_narrow<EPI, NT>(wd, ColsOffset{o0, o1, om, oov, r, r < n ? r : n - 1}, val, e, xin, cs);
-    e = e1;
-  } else if (fixed && wd > 8) {
-    fixed_sum = lp_row_sum_p16<EPI, COLT, NT>(col, val, e, wd, cb, xin, cs);
-    e = e1;
-  } else if (fixed) {
-    fixed_sum = lp_row_sum_narrow<EPI, NT>(wd, ColsStored<COLT, NT>{col, cb}, val, e, xin, cs);
-    e = e1;                               // nothing left for the general loops below
-  }
-  for (; e + STEP * (UNR - 1) < e1; e += STEP * UNR, k += WPS * UNR) {
-    int c[UNR];
-    double v[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      c[u] = (k + WPS * u < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e + STEP * u) : col[e + STEP * u]);
-      v[u] = (double)(NT ? __builtin_nontemporal_load(val + e + STEP * u) : val[e + STEP * u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) acc[u] += v[u] * ((EPI == EPI_PRE && cs) ? xin[c[u]] * cs[c[u]] : xin[c[u]]);
-  }
-  for (; e < e1; e += STEP, k += WPS) {
-    const int c0 = (k < cb.z ? cb.x : cb.y) + (int)(NT ? __builtin_nontemporal_load(col + e) : col[e]);
-    const double v0 = (double)(NT ? __builtin_nontemporal_load(val + e) : val[e]);
-    acc[0] += v0 * ((EPI == EPI_PRE && cs) ? xin[c0] * cs[c0] : xin[c0]);
-  }
-  double sum = fixed ? fixed_sum : (acc[0] + acc[1]) + (acc[2] + acc[3]);
-  if (WPS == 4) {
-    if (wv > 0) part[wv - 1][l] = sum;
-    __syncthreads();
-    if (wv > 0) return;
-    sum = (sum + part[0][l]) + (part[1][l] + part[2][l]);
-  }
-  if (r >= n) return;
-  if (EPI == EPI_NONE) {
-    y[r] = sum;
-  } else if (EPI == EPI_RES) {
-    y[r] = e_b - sum;
-  } else if (EPI == EPI_ADD) {
-    y[r] = e_z + sum;
-  } else if (EPI == EPI_JAC) {
-    y[r] = e_x + w * e_d * (e_b - sum);
-  } else if (EPI == EPI_POST) {
-    y[r] = w * e_d * (e_z + e_b) + sum;
-  } else {  // EPI_PRE
-    if (z) z[r] = w * e_d * e_b;
-    y[r] = e_b - w * sum;
-  }
+  spmv_sell_slice<float, COLT, EPI, WPS, NT, OFFS, SliceLp>(sl_ptr, nslice, n, col, val, base, x, y, b, z, dinv, w, cs, omask,
+                                                            orec);
+}
+struct LpArgs {
+  const double* x;
+  double* y;
+  const double* b;
+  double* z;
+  const double* dinv;
+  double w;
+  const double* cs;
+};
+template <int EPI, int WPS, typename COLT, bool OFFS>
+static void spmv_lp_launch_as(const Csr& a, const COLT* col, bool nt, const LpArgs& v) {
+  const int grid = 8 * (WPS == 4 ? (a.nslice + 7) / 8 : ((a.nslice + 3) / 4 + 7) / 8);
+  const unsigned char* om = OFFS ? a.off_mask : nullptr;
+  const int* orec = OFFS ? a.off_rec : nullptr;
+  if (nt)
+    hipLaunchKernelGGL((k_spmv_sell_lp<EPI, WPS, COLT, true, OFFS>), dim3(grid), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n,
+                       col, a.lp_val, a.lp_base, v.x, v.y, v.b, v.z, v.dinv, v.w, v.cs, om, orec);
+  else
+    hipLaunchKernelGGL((k_spmv_sell_lp<EPI, WPS, COLT, false, OFFS>), dim3(grid), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n,
+                       col, a.lp_val, a.lp_base, v.x, v.y, v.b, v.z, v.dinv, v.w, v.cs, om, orec);
 }
 template <int EPI>
 static void spmv_lp_launch(const Csr& a, const double* x, double* y, const double* b, double* z, const double* dinv, double w) {
@@ -2697,39 +2551,25 @@ static void spmv_lp_launch(const Csr& a, const double* x, double* y, const doubl
   constexpr int nvec = EPI == EPI_NONE ? 2 : (EPI == EPI_POST ? 5 : (EPI == EPI_JAC ? 4 : 3));
   // Offset-coded slices stream no columns: 4 per stored entry + 64 mask bytes + a 32-byte record per slice.
   const double ebytes = a.lp_col ? 6.0 : 8.0;
-  const bool offs = g_sell_offsets && a.off_mask && a.off_rec && a.lp_col && !sell_wide(a);
+  const bool wide = sell_wide(a);
+  const bool offs = g_sell_offsets && a.off_mask && a.off_rec && a.lp_col && !wide;
   const double obytes = offs ? 96.0 * a.off_coded - 2.0 * (double)a.off_nnz : 0.0;
   ProfScope prof(PROF_LP, (double)a.sl_nnz * ebytes >= 32e6,
                  (double)a.sl_nnz * ebytes + obytes + 4.0 * a.nslice + 8.0 * nvec * (double)a.n, 2.0 * (double)a.nnz);
-  const double* cs = (EPI == EPI_PRE && !a.col_scaled) ? dinv : nullptr;
-  const int per = (a.nslice + 7) / 8;
-  const int perw = ((a.nslice + 3) / 4 + 7) / 8;
   static const bool nt_off = getenv("GENEO_LP_NO_NT") != nullptr;
   const bool nt = !nt_off && (double)a.sl_nnz * ebytes >= 24e6;
-#define LP_LAUNCH2(WPS, COLT, colp, grid, NT)                                                                          \
-  hipLaunchKernelGGL((k_spmv_sell_lp<EPI, WPS, COLT, NT>), dim3(grid), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n, colp, \
-                     a.lp_val, a.lp_base, x, y, b, z, dinv, w, cs)
-#define LP_LAUNCH(WPS, COLT, colp, grid)          \
-  do {                                            \
-    if (nt) LP_LAUNCH2(WPS, COLT, colp, grid, true); \
-    else LP_LAUNCH2(WPS, COLT, colp, grid, false);   \
-  } while (0)
-  if (sell_wide(a)) {
-    if (a.lp_col) LP_LAUNCH(4, unsigned short, a.lp_col, per * 8);
-    else LP_LAUNCH(4, int, a.sl_col, per * 8);
+  const LpArgs v{x, y, b, z, dinv, w, (EPI == EPI_PRE && !a.col_scaled) ? dinv : nullptr};
+  // slice owner (workgroup for wide slices) x columns (offset-coded + 16-bit, 16-bit, 32-bit)
+  if (wide) {
+    if (a.lp_col) spmv_lp_launch_as<EPI, 4, unsigned short, false>(a, a.lp_col, nt, v);
+    else spmv_lp_launch_as<EPI, 4, int, false>(a, a.sl_col, nt, v);
+  } else if (offs) {
+    spmv_lp_launch_as<EPI, 1, unsigned short, true>(a, a.lp_col, nt, v);
+  } else if (a.lp_col) {
+    spmv_lp_launch_as<EPI, 1, unsigned short, false>(a, a.lp_col, nt, v);
   } else {
-    if (offs) {
-      if (nt)
-        hipLaunchKernelGGL((k_spmv_sell_lp<EPI, 1, unsigned short, true, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
-                           a.nslice, a.n, a.lp_col, a.lp_val, a.lp_base, x, y, b, z, dinv, w, cs, a.off_mask, a.off_rec);
-      else
-        hipLaunchKernelGGL((k_spmv_sell_lp<EPI, 1, unsigned short, false, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
-                           a.nslice, a.n, a.lp_col, a.lp_val, a.lp_base, x, y, b, z, dinv, w, cs, a.off_mask, a.off_rec);
-    } else if (a.lp_col) LP_LAUNCH(1, unsigned short, a.lp_col, perw * 8);
-    else LP_LAUNCH(1, int, a.sl_col, perw * 8);
+    spmv_lp_launch_as<EPI, 1, int, false>(a, a.sl_col, nt, v);
   }
-#undef LP_LAUNCH
-#undef LP_LAUNCH2
 }
 void spmv_lp(const Csr& a, const double* x, double* y) { spmv_lp_launch<EPI_NONE>(a, x, y, nullptr, nullptr, nullptr, 0.0); }
 void spmv_fused_lp(const Csr& a, int epi, const double* x, double* y, const double* b, double* z, const double* dinv, double w) {
@@ -2765,21 +2605,7 @@ __global__ __launch_bounds__(256) void k_spmv_vec(int n, const int* __restrict__
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
   if (!live || lane != 0) return;
-  if (EPI == EPI_NONE) {
-    y[r] = s;
-  } else if (EPI == EPI_RES) {
-    y[r] = b[r] - s;
-  } else if (EPI == EPI_ADD) {
-    y[r] = z[r] + s;
-  } else if (EPI == EPI_JAC) {
-    y[r] = x[r] + w * dinv[r] * (b[r] - s);
-  } else if (EPI == EPI_POST) {
-    y[r] = w * dinv[r] * (z[r] + b[r]) + s;
-  } else {
-    const double bb = b[r];
-    if (z) z[r] = w * dinv[r] * bb;
-    y[r] = bb - w * s;
-  }
+  epi_store_row<EPI>(r, s, epi_load_row<EPI>(r, b, z, dinv, x), w, y, z);
 }
 template <int EPI>
 static void spmv_vec_launch(const Csr& a, const double* x, double* y, const double* b, double* z, const double* dinv,
@@ -2805,24 +2631,36 @@ __global__ __launch_bounds__(256) void k_spmv_long(const int* __restrict__ rows,
 }
 
 static inline bool sell_nt(const Csr& a) { return (double)a.sl_nnz * 12.0 > 48e6; }
-static int g_sell_variant = 0;  // tuning variants of the sliced kernel (kind = 1 + 10 * variant)
+// Stream variants of the FP64 sliced kernel (kind = 1 + 10 * variant; GENEO_SELL_VARIANT): 0 = the default policy below,
+// 2 = cached stream, 3 = non-temporal stream, both over the 32-bit columns.  The other numbers named round-3 experiments
+// that are no longer built (profiles/HISTORY.md); they select the default policy.
+static int g_sell_variant = 0;
+static inline int sell_variant_of(int v) { return (v == 2 || v == 3) ? v : 0; }
 static int g_spmv_kind = -1;  // 0 = LDS row blocks, 1 = 64-row slices
 int spmv_kind() {
   if (g_spmv_kind < 0) {
     const char* e = getenv("GENEO_SPMV");
     g_spmv_kind = (e && std::string(e) == "lds") ? 0 : 1;
     const char* v = getenv("GENEO_SELL_VARIANT");
-    if (v) g_sell_variant = atoi(v);
+    if (v) g_sell_variant = sell_variant_of(atoi(v));
   }
   return g_spmv_kind;
 }
 const char* spmv_kernel_name() { return spmv_kind() == 0 ? "k_spmv_lds" : "k_spmv_sell"; }
 void set_spmv_kind(int kind) {     // kind = layout + 10 * variant + 100 * (1: ragged matrices keep the slices too)
   g_spmv_kind = (kind % 10) ? 1 : 0;
-  g_sell_variant = (kind / 10) % 10;
+  g_sell_variant = sell_variant_of((kind / 10) % 10);
   g_force_slices = (kind / 100) % 10 == 1;
 }
 
+template <bool NT, typename COLT, bool OFFS>
+static void spmv_sell_launch_as(const Csr& a, const COLT* col, const double* x, double* y) {
+  const int perw = ((a.nslice + 3) / 4 + 7) / 8;
+  constexpr bool C16 = !std::is_same<COLT, int>::value;
+  hipLaunchKernelGGL((k_spmv_sell<NT, COLT, OFFS>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n, col,
+                     a.sl_val, x, y, C16 ? a.lp_base : (const int*)nullptr, OFFS ? a.off_mask : (const unsigned char*)nullptr,
+                     OFFS ? a.off_rec : (const int*)nullptr);
+}
 void spmv(const Csr& a, const double* x, double* y) {
   if (a.n == 0) return;
   const int per = (a.nblk + 7) / 8;
@@ -2838,61 +2676,32 @@ void spmv(const Csr& a, const double* x, double* y) {
   } else if (sell_wide(a)) {
     spmv_wide_launch<EPI_NONE>(a, x, y, nullptr, nullptr, nullptr, 0.0);
   } else {
-    const int nwb = (a.nslice + 3) / 4;
-    const int perw = (nwb + 7) / 8;
-#define SELL_LAUNCH(U, N)                                                                                  \
-  hipLaunchKernelGGL((k_spmv_sell<U, N>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n, \
-                     a.sl_col, a.sl_val, x, y)
     // default policy: 4 k-steps in flight; the once-read (col,val) stream of a large matrix is marked
     // non-temporal so that it does not displace x and the multigrid vectors from L2 / Infinity Cache.
     // Measured in situ (126^3 bench, 190 MB matrix, every fine-level launch sampled): 38.5 us with NT,
     // 42.2 us without; back-to-back re-reads of the same matrix (a micro-benchmark, not the solver's
     // access pattern) prefer the cached stream, which is why small (coarse-level) matrices keep it.
-    int variant = g_sell_variant;
-    if (variant == 0 && g_sell_offsets && a.off_mask && a.off_rec && a.lp_col && a.lp_base) {
-      // offset-coded columns: 8 B per entry + 1.5 B per row in the coded slices, the 16-bit stream in the others; the
-      // accumulation order of the default kernel (the paths agree to the bit).  A change of dispatch for SMALL coded
-      // matrices too: below the sell_nt size they used to run <4, false, int> on the 32-bit columns (the 16-bit FP64 form was
-      // for large matrices only); their few slices that are not coded now read lp_col -- same entries, same order, same sums.
-      if (sell_nt(a))
-        hipLaunchKernelGGL((k_spmv_sell<4, true, unsigned short, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
-                           a.nslice, a.n, a.lp_col, a.sl_val, x, y, a.lp_base, a.off_mask, a.off_rec);
-      else
-        hipLaunchKernelGGL((k_spmv_sell<4, false, unsigned short, true>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr,
-                           a.nslice, a.n, a.lp_col, a.sl_val, x, y, a.lp_base, a.off_mask, a.off_rec);
-      if (a.nlong > 0)
-        hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val, x, y);
-      return;
+    const bool nt = g_sell_variant ? g_sell_variant == 3 : sell_nt(a);
+    // offset-coded columns: 8 B per entry + 1.5 B per row in the coded slices, the 16-bit stream in the others; the
+    // accumulation order of the default kernel (the paths agree to the bit).  A change of dispatch for SMALL coded
+    // matrices too: below the sell_nt size they used to run <false, int> on the 32-bit columns (the 16-bit FP64 form was
+    // for large matrices only); their few slices that are not coded now read lp_col -- same entries, same order, same sums.
+    const bool c16 = g_sell_variant == 0 && a.lp_col && a.lp_base;
+    const bool offs = c16 && g_sell_offsets && a.off_mask && a.off_rec;
+    if (offs) {
+      if (nt) spmv_sell_launch_as<true, unsigned short, true>(a, a.lp_col, x, y);
+      else spmv_sell_launch_as<false, unsigned short, true>(a, a.lp_col, x, y);
+    } else if (c16 && nt) {
+      // 16-bit column offsets are available: 10 B per entry of a large matrix, in the accumulation order of the
+      // 32-bit-column kernel (the two paths agree to the bit)
+      spmv_sell_launch_as<true, unsigned short, false>(a, a.lp_col, x, y);
+    } else if (nt) {
+      spmv_sell_launch_as<true, int, false>(a, a.sl_col, x, y);
+    } else {
+      spmv_sell_launch_as<false, int, false>(a, a.sl_col, x, y);
     }
-    if ((variant == 0 || variant >= 5) && a.lp_col && a.lp_base && sell_nt(a)) {   // 16-bit column offsets are available: 10 B per entry
-      // Default: 4 steps in flight + one-at-a-time tail (the same accumulation order as the 32-bit-column kernel: the two
-      // paths agree to the bit).  GENEO_SELL_VARIANT=5 / 7: the predicated eight-step form (round-3 experiment: 20 % faster
-      // back to back on an evicted cache, no difference in situ -- 5037 vs 5017 GB/s -- and a different rounding).
-      if (variant == 0 || variant == 6)
-        hipLaunchKernelGGL((k_spmv_sell<4, true, unsigned short>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice,
-                           a.n, a.lp_col, a.sl_val, x, y, a.lp_base);
-      else if (variant == 7)     // predicated form without the non-temporal hint
-        hipLaunchKernelGGL((k_spmv_sell_p8<false, unsigned short>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice,
-                           a.n, a.lp_col, a.sl_val, x, y, a.lp_base);
-      else
-        hipLaunchKernelGGL((k_spmv_sell_p8<true, unsigned short>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice,
-                           a.n, a.lp_col, a.sl_val, x, y, a.lp_base);
-      if (a.nlong > 0)
-        hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val, x, y);
-      return;
-    }
-    if (variant == 0) variant = sell_nt(a) ? 3 : 2;
-    switch (variant) {
-      case 1: SELL_LAUNCH(2, true); break;
-      case 2: SELL_LAUNCH(4, false); break;
-      case 3: SELL_LAUNCH(4, true); break;
-      case 4: SELL_LAUNCH(7, true); break;
-      default: SELL_LAUNCH(2, false); break;
-    }
-#undef SELL_LAUNCH
     if (a.nlong > 0)
-      hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val,
-                         x, y);
+      hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val, x, y);
   }
 }
 
@@ -2965,21 +2774,15 @@ __global__ __launch_bounds__(256) void k_spmm(int n, const int* __restrict__ row
       if (live && j < m) {
         double sacc = s0 + s1;
         if (post) sacc *= post[r];
-        if (EPI == EPI_NONE) {
-          Y[r * ldy + j] = sacc;
-        } else if (EPI == EPI_RES) {
-          Y[r * ldy + j] = B[r * ldb + j] - sacc;
-        } else if (EPI == EPI_ADD) {
-          Y[r * ldy + j] = Z[r * ldz + j] + sacc;
-        } else if (EPI == EPI_JAC) {
-          Y[r * ldy + j] = X[r * ldx + j] + w * dinv[r] * (B[r * ldb + j] - sacc);
-        } else if (EPI == EPI_POST) {
-          Y[r * ldy + j] = w * dinv[r] * (Z[r * ldz + j] + B[r * ldb + j]) + sacc;
-        } else {  // EPI_PRE: X = B, pre = dinv
-          const double bb = B[r * ldb + j];
-          if (Z) Z[r * ldz + j] = w * dinv[r] * bb;
-          Y[r * ldy + j] = bb - w * sacc;
-        }
+        // EPI_PRE: X = B, pre = dinv
+        double e_b = 0.0, e_z = 0.0, e_d = 0.0, e_x = 0.0, zv = 0.0;
+        if (EpiReads<EPI>::b) e_b = B[r * ldb + j];
+        if (EpiReads<EPI>::z) e_z = Z[r * ldz + j];
+        if (EpiReads<EPI>::d(Z)) e_d = dinv[r];
+        if (EpiReads<EPI>::x) e_x = X[r * ldx + j];
+        const double yv = epi_apply<EPI>(sacc, e_b, e_z, e_d, e_x, w, zv);
+        if (EPI == EPI_PRE && Z) Z[r * ldz + j] = zv;
+        Y[r * ldy + j] = yv;
       }
     }
   }
@@ -3001,6 +2804,16 @@ __global__ __launch_bounds__(256) void k_spmm(int n, const int* __restrict__ row
 // neighbours: that window, not the whole block, is what the XCD's private 4 MiB L2 has to keep.  (Which XCD a group
 // lands on does not matter for correctness.)  sched == nullptr: slices in natural order.
 typedef double spmm_d2 __attribute__((ext_vector_type(2)));
+// the epilogue of the two columns a lane owns: epi_apply per component
+template <int EPI>
+__device__ __forceinline__ spmm_d2 epi_apply2(spmm_d2 sum, spmm_d2 e_b, spmm_d2 e_z, double e_d, spmm_d2 e_x, double w,
+                                              spmm_d2& zout) {
+  double z0 = 0.0, z1 = 0.0;
+  const double y0 = epi_apply<EPI>(sum.x, e_b.x, e_z.x, e_d, e_x.x, w, z0);
+  const double y1 = epi_apply<EPI>(sum.y, e_b.y, e_z.y, e_d, e_x.y, w, z1);
+  zout = spmm_d2{z0, z1};
+  return spmm_d2{y0, y1};
+}
 template <int LG, int U, int KW>
 __device__ __forceinline__ void spmm_sell_accum(const int* mc, const double* mv, int rl0, const double* __restrict__ Xq,
                                                 int ldx, spmm_d2* acc) {
@@ -3087,10 +2900,10 @@ __global__ __launch_bounds__(256) void k_spmm_sell(const int64_t* __restrict__ s
         e_b[u] = e_z[u] = e_x[u] = d2{0.0, 0.0};
         e_d[u] = 0.0;
         if (EPI != EPI_NONE && r < n) {
-          if (EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE) e_b[u] = *reinterpret_cast<const d2*>(B + r * ldb + 2 * q);
-          if (EPI == EPI_ADD || EPI == EPI_POST) e_z[u] = *reinterpret_cast<const d2*>(Z + r * ldz + 2 * q);
-          if (EPI == EPI_JAC) e_x[u] = *reinterpret_cast<const d2*>(X + r * ldx + 2 * q);
-          if (EPI == EPI_JAC || EPI == EPI_POST || (EPI == EPI_PRE && Z)) e_d[u] = dinv[r];
+          if (EpiReads<EPI>::b) e_b[u] = *reinterpret_cast<const d2*>(B + r * ldb + 2 * q);
+          if (EpiReads<EPI>::z) e_z[u] = *reinterpret_cast<const d2*>(Z + r * ldz + 2 * q);
+          if (EpiReads<EPI>::x) e_x[u] = *reinterpret_cast<const d2*>(X + r * ldx + 2 * q);
+          if (EpiReads<EPI>::d(Z)) e_d[u] = dinv[r];
         }
       }
 #pragma unroll
@@ -3099,21 +2912,9 @@ __global__ __launch_bounds__(256) void k_spmm_sell(const int64_t* __restrict__ s
         if (r >= n) continue;
         d2 a2 = acc[u];
         if (post) a2 *= post[r];
-        d2 out;
-        if (EPI == EPI_NONE) {
-          out = a2;
-        } else if (EPI == EPI_RES) {
-          out = e_b[u] - a2;
-        } else if (EPI == EPI_ADD) {
-          out = e_z[u] + a2;
-        } else if (EPI == EPI_JAC) {
-          out = e_x[u] + (w * e_d[u]) * (e_b[u] - a2);
-        } else if (EPI == EPI_POST) {
-          out = (w * e_d[u]) * (e_z[u] + e_b[u]) + a2;
-        } else {  // EPI_PRE: X = B, pre = dinv
-          if (Z) *reinterpret_cast<d2*>(Z + r * ldz + 2 * q) = (w * e_d[u]) * e_b[u];
-          out = e_b[u] - w * a2;
-        }
+        d2 zv = d2{0.0, 0.0};     // EPI_PRE: X = B, pre = dinv
+        const d2 out = epi_apply2<EPI>(a2, e_b[u], e_z[u], e_d[u], e_x[u], w, zv);
+        if (EPI == EPI_PRE && Z) *reinterpret_cast<d2*>(Z + r * ldz + 2 * q) = zv;
         __builtin_nontemporal_store(out, reinterpret_cast<d2*>(Y + r * ldy + 2 * q));
       }
     }
@@ -3162,10 +2963,10 @@ __global__ __launch_bounds__(256) void k_spmm_sell_wide(const int64_t* __restric
       e_b[u] = e_z[u] = e_x[u] = d2{0.0, 0.0};
       e_d[u] = 0.0;
       if (EPI != EPI_NONE && r < n) {
-        if (EPI == EPI_RES || EPI == EPI_JAC || EPI == EPI_POST || EPI == EPI_PRE) e_b[u] = *reinterpret_cast<const d2*>(B + r * ldb + 2 * q);
-        if (EPI == EPI_ADD || EPI == EPI_POST) e_z[u] = *reinterpret_cast<const d2*>(Z + r * ldz + 2 * q);
-        if (EPI == EPI_JAC) e_x[u] = *reinterpret_cast<const d2*>(X + r * ldx + 2 * q);
-        if (EPI == EPI_JAC || EPI == EPI_POST || (EPI == EPI_PRE && Z)) e_d[u] = dinv[r];
+        if (EpiReads<EPI>::b) e_b[u] = *reinterpret_cast<const d2*>(B + r * ldb + 2 * q);
+        if (EpiReads<EPI>::z) e_z[u] = *reinterpret_cast<const d2*>(Z + r * ldz + 2 * q);
+        if (EpiReads<EPI>::x) e_x[u] = *reinterpret_cast<const d2*>(X + r * ldx + 2 * q);
+        if (EpiReads<EPI>::d(Z)) e_d[u] = dinv[r];
       }
     }
   };
@@ -3206,21 +3007,9 @@ __global__ __launch_bounds__(256) void k_spmm_sell_wide(const int64_t* __restric
     if (r >= n) continue;
     d2 a2 = acc[u];
     if (post) a2 *= post[r];
-    d2 out;
-    if (EPI == EPI_NONE) {
-      out = a2;
-    } else if (EPI == EPI_RES) {
-      out = e_b[u] - a2;
-    } else if (EPI == EPI_ADD) {
-      out = e_z[u] + a2;
-    } else if (EPI == EPI_JAC) {
-      out = e_x[u] + (w * e_d[u]) * (e_b[u] - a2);
-    } else if (EPI == EPI_POST) {
-      out = (w * e_d[u]) * (e_z[u] + e_b[u]) + a2;
-    } else {  // EPI_PRE: X = B, pre = dinv
-      if (Z) *reinterpret_cast<d2*>(Z + r * ldz + 2 * q) = (w * e_d[u]) * e_b[u];
-      out = e_b[u] - w * a2;
-    }
+    d2 zv = d2{0.0, 0.0};     // EPI_PRE: X = B, pre = dinv
+    const d2 out = epi_apply2<EPI>(a2, e_b[u], e_z[u], e_d[u], e_x[u], w, zv);
+    if (EPI == EPI_PRE && Z) *reinterpret_cast<d2*>(Z + r * ldz + 2 * q) = zv;
     if (nt) __builtin_nontemporal_store(out, reinterpret_cast<d2*>(Y + r * ldy + 2 * q));
     else *reinterpret_cast<d2*>(Y + r * ldy + 2 * q) = out;
   }

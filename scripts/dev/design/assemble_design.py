@@ -26,7 +26,7 @@ Python prototype `geneo4petsc_amd/driver.py` it was ported from; `tests/test_dri
 `INFO:` lines character by character.  Lines 0, 1 and the solve line are byte-identical to `tst/dummy/*.ref`, line 2 keeps
 the token layout `tst/plot.py` parses with this build's solver names (`pcg-amg`, `lobpcg cholesky`).""")
 i2=body.index("**Fused LOBPCG update** (`k_lobpcg_update32`)")
-body = body[:i2] + ("**Two-latency forms of the sliced SpMV kernels** (round 4: `spmv_row_sum_fixed`, `lp_row_sum_fixed`, `lp_row_sum_p16`).  A wave of the\n"
+body = body[:i2] + ("**Two-latency forms of the sliced SpMV kernels** (round 4: `row_sum_fixed`, `lp_row_sum_p16`).  A wave of the\n"
  "wave-per-slice kernels holds ONE 64-row slice, so its run time is a chain of dependent memory latencies, not bandwidth; the\n"
  "4-step loop sends a 7-wide slice through one round of four and three one-at-a-time tail steps — eight latencies ((col, val) →\n"
  "gather, four times).  For slices of at most 8 entries (FP64 SpMV) / 16 entries (companions: the 12-wide post-smoothing\n"
