@@ -164,6 +164,9 @@ SYMBOLS = {
                                    C.c_int, c_dbl_p]),
     "GeneoTestPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
     "PCGenEOGetCoarseInfo": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "PCGenEOGetLocalSolverInfo": (C.c_int, [C.c_void_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, C.c_int]),
+    "PCGenEOGetLocalSolverTable": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int]),
+    "PCGenEOGetLocalSolverCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
     "GeneoTestCoarseFactor": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
     "GeneoTestCoarseSolve": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int]),
     "GeneoTestCoarseElapsed": (C.c_int, [c_dbl_p, c_dbl_p]),

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "backend.h"
+#include "cheb_dev.h"
 
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
@@ -2703,6 +2704,50 @@ void spmv(const Csr& a, const double* x, double* y) {
     if (a.nlong > 0)
       hipLaunchKernelGGL(k_spmv_long, dim3(a.nlong), dim3(256), 0, g_stream, a.long_rows, a.rowptr, a.col, a.val, x, y);
   }
+}
+
+// r_out = r_in - A d (cheb_dev.h): k_spmv_sell with the residual epilogue on its output write -- the traversal, column
+// source (16-bit offsets, offset-coded slices) and summation order of bk::spmv, so the bits of spmv + axpy(r, -1, q).
+// Two residual buffers: the traversal's pointers are __restrict__, an in-place r would alias its b and y.
+template <bool NT, typename COLT, bool OFFS>
+__global__ __launch_bounds__(256) void k_spmv_sell_res(const int64_t* __restrict__ sl_ptr, int nslice, int n,
+                                                       const COLT* __restrict__ col, const double* __restrict__ val,
+                                                       const double* __restrict__ x, double* __restrict__ y,
+                                                       const double* __restrict__ b, const int* __restrict__ cbase,
+                                                       const unsigned char* __restrict__ omask,
+                                                       const int* __restrict__ orec) {
+  spmv_sell_slice<double, COLT, EPI_RES, 1, NT, OFFS, SliceSell>(sl_ptr, nslice, n, col, val, cbase, x, y, b, nullptr,
+                                                                 nullptr, 0.0, nullptr, omask, orec);
+}
+template <bool NT, typename COLT, bool OFFS>
+static void spmv_sell_res_launch_as(const Csr& a, const COLT* col, const double* x, double* y, const double* b) {
+  const int perw = ((a.nslice + 3) / 4 + 7) / 8;
+  constexpr bool C16 = !std::is_same<COLT, int>::value;
+  hipLaunchKernelGGL((k_spmv_sell_res<NT, COLT, OFFS>), dim3(perw * 8), dim3(256), 0, g_stream, a.sl_ptr, a.nslice, a.n,
+                     col, a.sl_val, x, y, b, C16 ? a.lp_base : (const int*)nullptr,
+                     OFFS ? a.off_mask : (const unsigned char*)nullptr, OFFS ? a.off_rec : (const int*)nullptr);
+}
+bool cheb_residual(const Csr& a, const double* d, const double* r_in, double* r_out) {
+  if (a.n == 0) return true;
+  if (spmv_kind() != 1 || a.vec_lpr > 0 || a.nlong > 0 || sell_wide(a) || !a.sl_ptr) return false;
+  if (r_out == r_in || r_out == d) return false;
+  const double abytes = (double)a.nnz * 12.0 + ((double)a.n + 1.0) * 4.0 + (double)a.n * 24.0;   // spmv's + r_in
+  ProfScope prof(PROF_SPMV, a.fine || (g_prof_min_bytes > 0.0 && abytes >= g_prof_min_bytes), abytes, 2.0 * (double)a.nnz);
+  // the dispatch of bk::spmv
+  const bool nt = g_sell_variant ? g_sell_variant == 3 : sell_nt(a);
+  const bool c16 = g_sell_variant == 0 && a.lp_col && a.lp_base;
+  const bool offs = c16 && g_sell_offsets && a.off_mask && a.off_rec;
+  if (offs) {
+    if (nt) spmv_sell_res_launch_as<true, unsigned short, true>(a, a.lp_col, d, r_out, r_in);
+    else spmv_sell_res_launch_as<false, unsigned short, true>(a, a.lp_col, d, r_out, r_in);
+  } else if (c16 && nt) {
+    spmv_sell_res_launch_as<true, unsigned short, false>(a, a.lp_col, d, r_out, r_in);
+  } else if (nt) {
+    spmv_sell_res_launch_as<true, int, false>(a, a.sl_col, d, r_out, r_in);
+  } else {
+    spmv_sell_res_launch_as<false, int, false>(a, a.sl_col, d, r_out, r_in);
+  }
+  return true;
 }
 
 // =============================================================================== CSR SpMM

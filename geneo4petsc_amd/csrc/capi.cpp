@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "../../include/geneo_c.h"
+#include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "core.h"
 #include "dense.h"
@@ -130,15 +131,16 @@ const char* PCGenEOGetName(PC pc) { return pc ? pc->name.c_str() : ""; }
 const char* PCGenEOGetOptionsString(PC pc) {
   if (!pc || !pc->ctx) return "";
   const geneo::Options& o = pc->ctx->opt;
-  char buf[1024];
+  char buf[1280];
   snprintf(buf, sizeof(buf),
            "lvl1ASM=%d;lvl1RAS=%d;lvl1SRAS=%d;lvl1ORAS=%d;lvl2=%d;hybrid=%d;effHybrid=%d;optim=%.17g;tau=%.17g;"
            "gamma=%.17g;cst=%d;cut=%d;noSyl=%d;offload=%d;eps_tol=%.17g;dls1_rtol=%.17g;dls1_pc=%s;els2_pc=%s;"
-           "ksp_type=%s;ksp_rtol=%.17g;ksp_atol=%.17g;ksp_max_it=%d;ksp_restart=%d",
+           "ksp_type=%s;ksp_rtol=%.17g;ksp_atol=%.17g;ksp_max_it=%d;ksp_restart=%d;"
+           "dls1_ksp_type=%s;dls1_cheb_esteig_its=%d;dls1_cheb_safety=%.17g,%.17g",
            (int)o.lvl1ASM, (int)o.lvl1RAS, (int)o.lvl1SRAS, (int)o.lvl1ORAS, o.lvl2, (int)o.hybrid, (int)o.effHybrid,
            o.optim, o.tau, o.gamma, (int)o.cst, o.cut, (int)o.noSyl, (int)o.offload, o.eps_tol, o.dls1_rtol,
            o.dls1_pc.c_str(), o.els2_pc.c_str(), o.ksp_type.c_str(), o.ksp_rtol, o.ksp_atol, o.ksp_max_it,
-           o.ksp_restart);
+           o.ksp_restart, o.dls1_ksp.c_str(), o.dls1_cheb_esteig_its, o.dls1_cheb_safety_lo, o.dls1_cheb_safety_hi);
   pc->optstr = buf;
   return pc->optstr.c_str();
 }
@@ -176,6 +178,13 @@ const char* usageGenEO_c(void) {
          "  -els2_eps_tol / -els2_eps_nev / -els2_eps_max_it / -els2_eps_block / -els2_pc_type amg|cheb\n"
          "  -els2_cheb_degree / -els2_cheb_ratio\n"
          "  -dls1_ksp_rtol / -dls1_ksp_max_it / -dls1_pc_type amg|jacobi   local solves (batched PCG)\n"
+         "  -dls1_ksp_type cg|chebyshev   the local Krylov method (defaults to cg): batched V-cycle-PCG to -dls1_ksp_rtol, or a\n"
+         "                   fixed-degree Chebyshev iteration on the same V-cycle (needs -dls1_pc_type amg): no reductions, no\n"
+         "                   host polling, a fixed linear operator at any -dls1_ksp_rtol; the degree per subdomain is the\n"
+         "                   smallest k with 1 / T_k(sigma) <= -dls1_ksp_rtol, at most -dls1_ksp_max_it\n"
+         "  -dls1_cheb_esteig_its N   Lanczos steps of its eigenvalue-bound estimate (defaults to 16)\n"
+         "  -dls1_cheb_safety LO,HI   factors on the smallest and largest Ritz value (defaults to 0.9,1.1; only HI matters for\n"
+         "                   positive definiteness, LO for accuracy alone)\n"
          "  -dls1_amg_precision single|double   storage of the matrices its V-cycle reads (arithmetic and vectors: double)\n"
          "  -dls1_amg_strength T / -els2_amg_strength T   aggregation from level 1 on ties |a_ij| >= T 0.5^l sqrt(a_ii a_jj) only\n"
          "  -amg_coarse_size / -amg_smooth_degree / -amg_smooth_ratio / -amg_max_levels\n"
@@ -405,6 +414,44 @@ int PCGenEOGetLocalDims(PC pc, int* k, int cap) {
   return (int)v.size();
 }
 
+int PCGenEOGetLocalSolverInfo(PC pc, double* lo, double* hi, int* its, double* achieved, int cap) {
+  if (!pc || !pc->ctx) return -1;
+  const geneo::PC& c = *pc->ctx;
+  const int n = (int)c.cheb_its.size();
+  for (int i = 0; i < n && i < cap; ++i) {
+    if (lo) lo[i] = c.cheb_lo[i];
+    if (hi) hi[i] = c.cheb_hi[i];
+    if (its) its[i] = c.cheb_its[i];
+    if (achieved) achieved[i] = i < (int)c.cheb_achieved.size() ? c.cheb_achieved[i] : 0.0;
+  }
+  return n;
+}
+
+int PCGenEOGetLocalSolverTable(PC pc, double* coef, int cap) {
+  if (!pc || !pc->ctx) return -1;
+  const int K = pc->ctx->cheb_steps_per_solve();
+  if (coef && K > 0) {
+    try {
+      const std::vector<double> t = pc->ctx->cheb_table();
+      std::copy_n(t.begin(), std::min<size_t>(t.size(), (size_t)std::max(0, cap)), coef);
+    } catch (std::exception& e) {
+      pcfail(pc, e.what());
+      return -1;
+    }
+  }
+  return K;
+}
+
+int PCGenEOGetLocalSolverCounters(PC pc, long long* solves, long long* graph_launches, long long* fused_residuals) {
+  if (!pc || !pc->ctx) return -1;
+  long long v[3];
+  pc->ctx->cheb_counters(&v[0], &v[1], &v[2]);
+  if (solves) *solves = v[0];
+  if (graph_launches) *graph_launches = v[1];
+  if (fused_residuals) *fused_residuals = v[2];
+  return pc->ctx->cheb_steps_per_solve();
+}
+
 PetscErrorCode PCGenEOGetCoarseInfo(PC pc, int* dimE, int* factor_on_device, int* solve_kind, int* block) {
   if (!pc || !pc->ctx) return 1;
   pc->ctx->coarse_info(dimE, factor_on_device, solve_kind, block);
@@ -536,7 +583,13 @@ PetscErrorCode GeneoSetMFMA(int enable) {
   bk::set_mfma(enable != 0);
   return 0;
 }
-PetscErrorCode GeneoSetKernelVariant(const char* name, int value) { return bk::set_variant(name, value) ? 0 : 1; }
+PetscErrorCode GeneoSetKernelVariant(const char* name, int value) {
+  if (name && std::string(name) == "cheb_fused") {     // a choice of core.cpp, not of the backend: bk::cheb_dir / bk::cheb_residual or their composed forms
+    geneo::set_cheb_fused(value);
+    return 0;
+  }
+  return bk::set_variant(name, value) ? 0 : 1;
+}
 
 // ---- stand-alone kernels --------------------------------------------------------------------
 PetscErrorCode GeneoSpmvCreate(const GeneoCsr* a, GeneoSpmv* h) {
@@ -870,6 +923,9 @@ int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* co
       else if (k == "block_residual_norms")
         bk::block_residual_norms(c, d(1), I[1], d(2), I[2], d(3), I[3], d(4), I[4], d(5), d(6));
       else if (k == "block_colscale") bk::block_colscale(c, d(1), I[1], I[2], d(2));
+      else if (k == "cheb_dir")      // (GeneoSetKernelVariant("cheb_fused", 0): the composed form of core.cpp)
+        rc = (geneo::cheb_fused() ? bk::cheb_dir(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6))
+                                  : geneo::cheb_dir_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6))) ? 1 : 0;
       else if (k == "block_init")
         bk::block_init(c, d(1), I[1], I[2], ip(2), ((uint64_t)(uint32_t)I[4] << 32) | (uint64_t)(uint32_t)I[3]);
       else if (k == "block_extract") bk::block_extract(c, d(1), I[1], I[2], d(2), ip(3), ip(4), lp(5), d(6));

@@ -35,6 +35,7 @@
 #include <thread>
 
 #include "amg.h"
+#include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "dense.h"
 
@@ -43,6 +44,88 @@
 namespace bk {
 __attribute__((weak)) bool coarse_factor(const double*, int, int, double*, double*, int*) { return false; }
 __attribute__((weak)) bool coarse_solve(const double*, const double*, int, int, double*) { return false; }
+}  // namespace bk
+
+// The step kernel of the Chebyshev local solver (cheb_dev.h) composed of backend.h primitives: the definition a backend
+// without cheb_dev.hip links (the host twin), and on the GPU the comparison GeneoSetKernelVariant("cheb_fused", 0) selects.
+// d = fl(fl(a z) + fl(b d)): block_colscale rounds both products, axpy with factor 1 adds them with one rounding -- the
+// expression the fused kernel evaluates with contraction off.  Its scratch (ChebWork: one vector, the de-interleaved
+// coefficients and their gather indices) belongs to the caller: a PC allocates its own in setup_cheb and frees it in
+// cheb_release, so nothing is allocated inside a graph capture and nothing is shared between PCs.
+namespace geneo {
+static std::atomic<int> g_cheb_fused{1};
+void set_cheb_fused(int on) { g_cheb_fused = on ? 1 : 0; }
+int cheb_fused() { return g_cheb_fused.load(); }
+
+void ChebWork::alloc(int n_, int ns_) {
+  release();
+  if (n_ <= 0 || ns_ <= 0) return;
+  t = (double*)bk::alloc(sizeof(double) * (size_t)n_);
+  ab = (double*)bk::alloc(sizeof(double) * 2 * (size_t)ns_);
+  idx = (int*)bk::alloc(sizeof(int) * 2 * (size_t)ns_);
+  std::vector<int> h(2 * (size_t)ns_);
+  for (int s = 0; s < ns_; ++s) {
+    h[s] = 2 * s;                // a_s ...
+    h[ns_ + s] = 2 * s + 1;      // ... then b_s
+  }
+  bk::h2d(idx, h.data(), sizeof(int) * h.size());
+  n = n_;
+  ns = ns_;
+}
+void ChebWork::release() {
+  bk::dfree(t);
+  bk::dfree(ab);
+  bk::dfree(idx);
+  t = ab = nullptr;
+  idx = nullptr;
+  n = ns = 0;
+}
+
+bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                       const double* dscale, double* out, const ChebWork& w) {
+  const int n = c.n, ns = c.nsub;
+  if (n <= 0 || ns <= 0) return true;
+  if (w.n < n || w.ns != ns) throw std::runtime_error("cheb_dir_composed: scratch of another size");
+  bk::gather(w.ab, coef_k, w.idx, ns);                  // a_0 .. a_{ns-1}
+  bk::gather(w.ab + ns, coef_k, w.idx + ns, ns);        // b_0 .. b_{ns-1}
+  if (flags & 1) {
+    bk::copy(d, z, n);
+    bk::block_colscale(c, d, 1, 1, w.ab);
+    bk::copy(x, d, n);
+  } else {
+    bk::copy(w.t, z, n);
+    bk::block_colscale(c, w.t, 1, 1, w.ab);
+    bk::block_colscale(c, d, 1, 1, w.ab + ns);
+    bk::axpy(d, 1.0, w.t, n);
+    bk::axpy(x, 1.0, d, n);
+  }
+  if (flags & 2) {
+    if (dscale) bk::xmy(out, x, dscale, n);
+    else bk::copy(out, x, n);
+  }
+  return true;
+}
+
+// one call with scratch of its own (the weak bk::cheb_dir below and the primitive test): allocates, runs, waits, frees
+bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                            const double* dscale, double* out) {
+  struct Own {
+    ChebWork w;
+    ~Own() { w.release(); }
+  } own;
+  own.w.alloc(c.n, c.nsub);
+  const bool ok = cheb_dir_composed(c, coef_k, flags, z, d, x, dscale, out, own.w);
+  bk::sync();
+  return ok;
+}
+}  // namespace geneo
+
+namespace bk {
+__attribute__((weak)) bool cheb_dir(const Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                                    const double* dscale, double* out) {
+  return geneo::cheb_dir_composed_once(c, coef_k, flags, z, d, x, dscale, out);
+}
+__attribute__((weak)) bool cheb_residual(const Csr&, const double*, const double*, double*) { return false; }
 }  // namespace bk
 
 namespace geneo {
@@ -158,6 +241,27 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
   if (key == "-dls1_ksp_rtol") return dbl(o.dls1_rtol);
   if (key == "-dls1_ksp_max_it") return integer(o.dls1_max_it);
   if (key == "-dls1_check") return integer(o.dls1_check);
+  if (key == "-dls1_ksp_type") {
+    if (value != "cg" && value != "chebyshev") return "unsupported -dls1_ksp_type " + value;
+    o.dls1_ksp = value;
+    return "";
+  }
+  if (key == "-dls1_cheb_esteig_its") {
+    int v;
+    if (!to_int(value, v) || v < 2) return "invalid option -dls1_cheb_esteig_its, " + value + " is not an integer >= 2";
+    o.dls1_cheb_esteig_its = v;
+    return "";
+  }
+  if (key == "-dls1_cheb_safety") {
+    const size_t c = value.find(',');
+    double lo, hi;
+    if (c == std::string::npos || !to_double(value.substr(0, c), lo) || !to_double(value.substr(c + 1), hi) ||
+        !(lo > 0.0) || !(hi > 0.0) || !std::isfinite(lo) || !std::isfinite(hi))
+      return "invalid option -dls1_cheb_safety, " + value + " is not lo,hi with two positive factors";
+    o.dls1_cheb_safety_lo = lo;
+    o.dls1_cheb_safety_hi = hi;
+    return "";
+  }
   if (key == "-dls1_pc_type") {
     if (value != "amg" && value != "jacobi") return "unsupported -dls1_pc_type " + value;
     o.dls1_pc = value;
@@ -266,6 +370,7 @@ void PC::free_all() {
   cg_graphs.clear();
   cg_graph_failed = false;
   cg_long_len = 0;
+  cheb_release();
   delete amg1;
   delete amgN;
   amg1 = amgN = nullptr;
@@ -651,6 +756,20 @@ int PC::finish_amg1() {
     fprintf(stderr, "[amg] level-1 hierarchy on its own thread and stream (%s): %.3f s%s; waited %.3f s for it\n",
             p->on_device ? "device products, host aggregation" : "host products", p->res.secs,
             p->on_device ? "" : (" + upload " + std::to_string(p->upload_secs) + " s").c_str(), waited);
+  if (opt.dls1_ksp == "chebyshev" && !eig_only) {     // bounds, coefficient table and verification solve of the Chebyshev local solver
+    const auto tc = clk::now();
+    int rc = 1;
+    try {
+      rc = setup_cheb();
+    } catch (std::exception& e) {
+      rc = fail(e.what());
+    }
+    if (rc) {
+      cheb_release();
+      return rc;
+    }
+    info.lvl1SetupMinvTimeLoc += secs(tc, clk::now());
+  }
   return 0;
 }
 
@@ -748,6 +867,8 @@ int PC::setup_prepare() {
   if (!err.empty()) return fail(err);
   if (opt.lvl2 == 2 && !opt.lvl1ORAS)
     return fail("GenEO-2 needs the Robin matrix: use -geneo_lvl ORAS,2 or SORAS,2 (geneo.cpp:1283 takes pcARobLoc)");
+  if (opt.dls1_ksp == "chebyshev" && opt.dls1_pc != "amg")
+    return fail("GenEO preconditioner: -dls1_ksp_type chebyshev needs -dls1_pc_type amg (its bounds are those of the V-cycle-preconditioned operator)");
   if (N <= 0) return fail("GenEO preconditioner: empty problem");
   if (int rc = build_layout()) return rc;
   if (getenv("GENEO_DEBUG")) fprintf(stderr, "[setup] %-28s %.3f s\n", "layout (maps, R^T, work vectors)", secs(t0, clk::now()));
@@ -1162,6 +1283,10 @@ void PC::matmult_block(const double* X, double* Y, int w, double* WL, double* xe
 // [D] M^-1 [D] on the concatenated local space: one independent Jacobi-PCG per subdomain,
 // all subdomains advanced by the same launches (geneo.cpp:1991-2002 with MUMPS replaced).
 void PC::local_solve(double* wL) {
+  if (opt.dls1_ksp == "chebyshev") {
+    local_solve_cheb(wL);
+    return;
+  }
   if (opt.lvl1RAS) bk::xmy(wL, wL, d_D, nL);
   const int ns = (int)subs.size();
   const bool use_amg = (opt.dls1_pc == "amg") && amg1;
@@ -1282,6 +1407,245 @@ void PC::local_solve(double* wL) {
   if (!done) throw std::runtime_error("GenEO - solve KO: dls1 (KSP_DIVERGED_ITS)");
   if (opt.lvl1SRAS) bk::xmy(wL, x, d_D, nL);
   else bk::copy(wL, x, nL);
+}
+
+// ---- Chebyshev local solver (-dls1_ksp_type chebyshev) ---------------------------------------------------------------
+// x = p_k(V A) V b per subdomain: V the V-cycle of the level-1 hierarchy, p_k the Chebyshev polynomial of [lo_s, hi_s].
+// A fixed linear operator, symmetric whenever V is and positive definite as long as hi_s bounds the spectrum of V A
+// from above, whatever -dls1_ksp_rtol: no reductions, no host polling, one chain of launches of known length.
+void PC::cheb_release() {
+  if (cheb_graph) bk::graph_destroy(cheb_graph);
+  cheb_graph = nullptr;
+  cheb_graph_failed = false;
+  cheb_graph_wL = nullptr;
+  cheb_graph_fused = -1;
+  bk::dfree(d_cheb_coef);
+  d_cheb_coef = nullptr;
+  cheb_work.release();
+  cheb_K = 0;
+  cheb_solves = 0;
+  cheb_graph_launches = cheb_res_fused = 0;
+  cheb_graph_res = 0;
+  cheb_lo.clear();
+  cheb_hi.clear();
+  cheb_achieved.clear();
+  cheb_its.clear();
+}
+
+std::vector<double> PC::cheb_table() const {
+  std::vector<double> t((size_t)cheb_K * subs.size() * 2);
+  if (!t.empty() && d_cheb_coef) bk::d2h(t.data(), d_cheb_coef, sizeof(double) * t.size());
+  return t;
+}
+
+// Saad's recurrence (Iterative Methods, Alg. 12.1) on [lo, hi]: step k is d = a_k z + b_k d, rows k >= its are (0, 0)
+static void cheb_coefficients(double lo, double hi, int its, int K, int ns, int s, std::vector<double>& coef) {
+  const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo);
+  double rho = delta / theta;
+  for (int k = 0; k < K; ++k) {
+    double a = 0.0, b = 0.0;
+    if (k == 0) {
+      a = 1.0 / theta;
+    } else if (k < its) {
+      const double rho1 = 1.0 / (2.0 * theta / delta - rho);
+      a = 2.0 * rho1 / delta;
+      b = rho1 * rho;
+      rho = rho1;
+    }
+    coef[((size_t)k * ns + s) * 2] = a;
+    coef[((size_t)k * ns + s) * 2 + 1] = b;
+  }
+}
+
+// Bounds, degrees and the coefficient table, then one verification solve.  Runs once amg1 exists (finish_amg1).
+int PC::setup_cheb() {
+  cheb_release();
+  const int ns = (int)subs.size();
+  if (!amg1) return fail("GenEO preconditioner: -dls1_ksp_type chebyshev needs the level-1 hierarchy (-dls1_pc_type amg)");
+  if (ns == 0 || nL == 0) return 0;      // a rank without rows: local_solve_cheb has nothing to do there either
+  const int nlz = opt.dls1_cheb_esteig_its;
+  if (!(opt.dls1_cheb_safety_lo > 0.0) || !(opt.dls1_cheb_safety_hi > 0.0))
+    return fail("GenEO preconditioner: -dls1_cheb_safety needs two positive factors");
+  // Start vector: column 1 of the counter-based start block (column 0 is the constant vector): a function of the
+  // subdomain's global id and the local row alone, so a subdomain's bounds do not depend on its neighbours in the batch.
+  struct Tmp {
+    double *blk = nullptr, *rhs = nullptr, *nrm = nullptr;
+    ~Tmp() { bk::dfree(blk); bk::dfree(rhs); bk::dfree(nrm); }
+  } tmp;
+  tmp.blk = (double*)bk::alloc(sizeof(double) * 2 * (size_t)nL);
+  tmp.rhs = (double*)bk::alloc(sizeof(double) * (size_t)nL);
+  tmp.nrm = (double*)bk::alloc(sizeof(double) * 2 * (size_t)ns);
+  bk::block_init(ch, tmp.blk, 2, 2, d_subgid, 0x63686562ull);
+  bk::block_axpby(tmp.rhs, 1, 1.0, tmp.blk + 1, 2, 0.0, nL, 1);
+  // Lanczos through PCG: single steps of the batched V-cycle-PCG of local_solve, direct launches, tol2 = 0 (nothing
+  // freezes before its residual is exactly zero); alpha and beta of every step come back from the scalar block.
+  std::vector<double> sc((size_t)8 * ns);
+  std::vector<std::vector<double>> al(ns), be(ns);
+  bk::cg_start(ch, d_cg_sc, d_xL, d_cg_r, d_cg_z, d_cg_p, tmp.rhs, nullptr);
+  amg1->vcycle(d_cg_r, 1, d_cg_z, 1, 1);
+  bk::seg_partial(ch, d_cg_r, d_cg_z, 1);
+  bk::cg_set_rz(ch, d_cg_sc);
+  bk::copy(d_cg_p, d_cg_z, nL);
+  int parity = 0;
+  for (int k = 0; k < nlz; ++k) {
+    bk::spmv(dirL, d_cg_p, d_cg_q);
+    bk::seg_pap(ch, d_cg_p, d_cg_q);
+    bk::cg_update(ch, d_cg_sc, parity, d_xL, d_cg_r, d_cg_z, d_cg_p, d_cg_q, nullptr);
+    amg1->vcycle(d_cg_r, 1, d_cg_z, 1, 1);
+    bk::seg_partial(ch, d_cg_r, d_cg_z, 1);
+    bk::cg_direction(ch, d_cg_sc, parity, d_cg_p, d_cg_z, 0.0);
+    parity ^= 1;
+    bk::d2h(sc.data(), d_cg_sc, sizeof(double) * 8 * ns);
+    for (int s = 0; s < ns; ++s) {
+      al[s].push_back(sc[(size_t)s * 8 + 4]);
+      be[s].push_back(sc[(size_t)s * 8 + 5]);
+    }
+  }
+  cheb_lo.assign(ns, 0.0);
+  cheb_hi.assign(ns, 0.0);
+  cheb_its.assign(ns, 0);
+  int K = 0;
+  for (int s = 0; s < ns; ++s) {
+    // the recurrence ends at the first alpha that is not a positive number (an off-diagonal that is not one ends it too)
+    int m = 0;
+    while (m < nlz && std::isfinite(al[s][m]) && al[s][m] > 0.0) {
+      ++m;
+      if (!(std::isfinite(be[s][m - 1]) && be[s][m - 1] >= 0.0)) break;
+    }
+    if (m < 2)
+      return fail("GenEO preconditioner: -dls1_ksp_type chebyshev: the bound estimate of subdomain " + std::to_string(subs[s].gid) +
+                  " broke down after " + std::to_string(m) + " Lanczos step(s) (two are needed)");
+    std::vector<double> T((size_t)m * m, 0.0), w, v;
+    for (int k = 0; k < m; ++k) {
+      T[(size_t)k * m + k] = 1.0 / al[s][k] + (k > 0 ? be[s][k - 1] / al[s][k - 1] : 0.0);
+      if (k + 1 < m) T[(size_t)k * m + k + 1] = T[(size_t)(k + 1) * m + k] = std::sqrt(be[s][k]) / al[s][k];
+    }
+    dense::sym_eig(T, m, w, v);
+    const double tmin = *std::min_element(w.begin(), w.end()), tmax = *std::max_element(w.begin(), w.end());
+    const double lo = opt.dls1_cheb_safety_lo * tmin, hi = opt.dls1_cheb_safety_hi * tmax;
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.0) || !(hi > lo))
+      return fail("GenEO preconditioner: -dls1_ksp_type chebyshev: no usable bounds for subdomain " + std::to_string(subs[s].gid) +
+                  " (Ritz values " + std::to_string(tmin) + " .. " + std::to_string(tmax) + ", -dls1_cheb_safety " +
+                  std::to_string(opt.dls1_cheb_safety_lo) + "," + std::to_string(opt.dls1_cheb_safety_hi) + ")");
+    // degree: the smallest k with 1 / T_k(sigma) <= rtol (three-term recurrence of T_k), at most -dls1_ksp_max_it
+    const double sigma = (hi + lo) / (hi - lo);
+    const int kcap = std::max(1, opt.dls1_max_it);
+    int k = 1;
+    double t0 = 1.0, t1 = sigma;
+    while (k < kcap && !(1.0 / t1 <= opt.dls1_rtol)) {
+      const double t2 = 2.0 * sigma * t1 - t0;
+      t0 = t1;
+      t1 = t2;
+      ++k;
+    }
+    cheb_lo[s] = lo;
+    cheb_hi[s] = hi;
+    cheb_its[s] = k;
+    K = std::max(K, k);
+  }
+  std::vector<double> coef((size_t)K * ns * 2, 0.0);
+  for (int s = 0; s < ns; ++s) cheb_coefficients(cheb_lo[s], cheb_hi[s], cheb_its[s], K, ns, s, coef);
+  d_cheb_coef = (double*)bk::alloc(sizeof(double) * coef.size());
+  bk::h2d(d_cheb_coef, coef.data(), sizeof(double) * coef.size());
+  cheb_K = K;
+  cheb_work.alloc(nL, ns);
+  // Verification: one solve on the estimation right-hand side (no partition-of-unity scalings), ||b - A x|| / ||b|| per
+  // subdomain.  At or above 1 the polynomial grew: the upper bound lies below the spectrum.
+  bk::copy(d_wL, tmp.rhs, nL);
+  cheb_steps(d_wL, nullptr);
+  bk::spmv(dirL, d_wL, d_cg_q);
+  bk::axpy(d_cg_q, -1.0, tmp.rhs, nL);
+  bk::seg_dot(ch, d_cg_q, d_cg_q, tmp.nrm, 2, 0);
+  bk::seg_dot(ch, tmp.rhs, tmp.rhs, tmp.nrm, 2, 1);
+  std::vector<double> nr((size_t)2 * ns);
+  bk::d2h(nr.data(), tmp.nrm, sizeof(double) * 2 * ns);
+  cheb_achieved.assign(ns, 0.0);
+  for (int s = 0; s < ns; ++s) {
+    cheb_achieved[s] = std::sqrt(nr[(size_t)2 * s] / nr[(size_t)2 * s + 1]);
+    if (!(cheb_achieved[s] < 1.0))
+      return fail("GenEO preconditioner: -dls1_ksp_type chebyshev: the verification solve of subdomain " + std::to_string(subs[s].gid) +
+                  " did not reduce its residual (|r| / |b| = " + std::to_string(cheb_achieved[s]) +
+                  "): the upper eigenvalue bound is too low, raise hi of -dls1_cheb_safety lo,hi");
+  }
+  if (getenv("GENEO_DEBUG")) {
+    fprintf(stderr, "[dls1] chebyshev: K = %d;", K);
+    for (int s = 0; s < ns; ++s)
+      fprintf(stderr, " [%d: %.4g .. %.4g, k %d, %.2e]", subs[s].gid, cheb_lo[s], cheb_hi[s], cheb_its[s], cheb_achieved[s]);
+    fprintf(stderr, "\n");
+  }
+  return 0;
+}
+
+// The K steps: wL holds b on entry and x (dscale .* x) on return.  The residual travels between wL and d_cg_r (the fused
+// residual kernel writes out of place); the direction lives in d_cg_p, the solution in d_xL.
+int PC::cheb_steps(double* wL, const double* dscale) {
+  const int ns = (int)subs.size(), K = cheb_K;
+  const bool fused = g_cheb_fused.load() != 0;
+  const bool fusable = fused && bk::csr_fusable(dirL);
+  double *rc = wL, *ro = d_cg_r;
+  int nres = 0;
+  for (int k = 0; k < K; ++k) {
+    amg1->vcycle(rc, 1, d_cg_z, 1, 1);
+    const int flags = (k == 0 ? 1 : 0) | (k == K - 1 ? 2 : 0);
+    const double* ck = d_cheb_coef + (size_t)k * ns * 2;
+    if (fused) bk::cheb_dir(ch, ck, flags, d_cg_z, d_cg_p, d_xL, dscale, wL);
+    else cheb_dir_composed(ch, ck, flags, d_cg_z, d_cg_p, d_xL, dscale, wL, cheb_work);
+    if (k == K - 1) break;
+    if (fusable && bk::cheb_residual(dirL, d_cg_p, rc, ro)) {
+      std::swap(rc, ro);
+      ++nres;
+    } else {
+      bk::spmv(dirL, d_cg_p, d_cg_q);
+      bk::axpy(rc, -1.0, d_cg_q, nL);
+    }
+  }
+  return nres;
+}
+
+void PC::local_solve_cheb(double* wL) {
+  if (nL == 0 || subs.empty()) return;   // a rank without rows (setup_cheb made no table for it)
+  if (!d_cheb_coef || cheb_K <= 0 || !amg1) throw std::runtime_error("GenEO - solve KO: dls1 (-dls1_ksp_type chebyshev was not set up)");
+  if (opt.lvl1RAS) bk::xmy(wL, wL, d_D, nL);
+  const double* dscale = opt.lvl1SRAS ? d_D : nullptr;
+  // The whole solve is one linear chain of launches on one stream: captured once per PC into a HIP graph (recorded, not
+  // run, by the first solve, which goes out as direct launches) and replayed from the second solve on.  While bench.py's
+  // in-situ kernel timer runs, every 8th solve is launched directly so that its kernels are sampled, as the PCG path does.
+  const int fused = g_cheb_fused.load();
+  if (cheb_graph && (cheb_graph_wL != wL || cheb_graph_fused != fused)) {
+    bk::graph_destroy(cheb_graph);
+    cheb_graph = nullptr;
+  }
+  bool direct = false;
+  if (!cheb_graph) {
+    direct = true;
+    if (!cheb_graph_failed && bk::graph_capture_begin()) {
+      try {
+        cheb_graph_res = cheb_steps(wL, dscale);
+      } catch (...) {
+        bk::graph_capture_end();
+        cheb_graph_failed = true;
+        throw;
+      }
+      cheb_graph = bk::graph_capture_end();
+      cheb_graph_wL = wL;
+      cheb_graph_fused = fused;
+      if (!cheb_graph) cheb_graph_failed = true;
+    } else {
+      cheb_graph_failed = true;
+    }
+  } else if (bk::spmv_profiling() && (cheb_solves % 8 == 0)) {
+    direct = true;
+  }
+  ++cheb_solves;
+  if (direct) {
+    cheb_res_fused += cheb_steps(wL, dscale);
+  } else {
+    bk::graph_launch(cheb_graph);
+    ++cheb_graph_launches;
+    cheb_res_fused += cheb_graph_res;
+  }
+  info.dls1_iterations += cheb_K;
+  info.dls1_solves += 1;
 }
 
 // yE = E^-1 Z^T x, Z^T x taken from the already restricted xL; replicated host solve

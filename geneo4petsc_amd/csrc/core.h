@@ -63,6 +63,13 @@ struct Options {
   double dls1_rtol = 1e-12;
   int dls1_max_it = 20000;
   int dls1_check = 16;     // host convergence poll period (iterations; 4 with the AMG preconditioner)
+  // -dls1_ksp_type cg|chebyshev: the batched V-cycle-PCG above, or a fixed-degree Chebyshev iteration preconditioned by
+  // the same V-cycle (needs -dls1_pc_type amg): no reductions, no host polling, a fixed linear operator p(VA)V at any
+  // -dls1_ksp_rtol.  Per subdomain: eigenvalue bounds of VA from -dls1_cheb_esteig_its Lanczos steps, scaled by
+  // -dls1_cheb_safety lo,hi; the degree is the smallest k with 1 / T_k(sigma) <= -dls1_ksp_rtol (at most -dls1_ksp_max_it).
+  std::string dls1_ksp = "cg";
+  int dls1_cheb_esteig_its = 16;
+  double dls1_cheb_safety_lo = 0.9, dls1_cheb_safety_hi = 1.1;
   // inner preconditioners: "amg" = smoothed-aggregation V-cycle (default), "jacobi" / "cheb" = round-1 baseline
   std::string dls1_pc = "amg", els2_pc = "amg";
   int amg_coarse_size = 600, amg_smooth_degree = 1, amg_max_levels = 10;
@@ -101,6 +108,22 @@ struct Options {
 // returns "" on success, otherwise the error message (same texts as the reference)
 std::string parse_option(Options& o, const std::string& key, const std::string& value);
 std::string validate_options(const Options& o);
+// validation switch "cheb_fused": 1 (default) bk::cheb_dir and bk::cheb_residual, 0 the same step and residual update
+// composed of backend.h primitives (block_colscale, axpy, xmy, copy; spmv, axpy)
+void set_cheb_fused(int on);
+int cheb_fused();
+struct ChebWork {   // scratch of the composed step: one vector, the de-interleaved coefficients, their gather indices
+  double *t = nullptr, *ab = nullptr;
+  int* idx = nullptr;
+  int n = 0, ns = 0;
+  void alloc(int n, int ns);
+  void release();
+};
+// core.cpp: bk::cheb_dir's arithmetic from backend.h primitives, on the caller's scratch / on scratch of its own
+bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                       const double* dscale, double* out, const ChebWork& w);
+bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                            const double* dscale, double* out);
 
 struct Info {                 // public counters / timers of geneoContext (hdr/geneo.hpp:96-123)
   int estimDimELoc = 0, realDimELoc = 0, nicolaidesLoc = 0, dimE = 0;
@@ -166,9 +189,20 @@ class PC {
   int apply_q(const double* x_dev, double* y_dev);      // applyQ, geneo.cpp:1435
   // where E was factored and how E^-1 is applied (PCGenEOGetCoarseInfo)
   void coarse_info(int* dim, int* factor_on_device, int* solve_kind, int* block) const;
+  // Chebyshev local solver (-dls1_ksp_type chebyshev), per local subdomain: the bounds [lo, hi] of the V-cycle-
+  // preconditioned operator, the degree k_s and ||r_K|| / ||b|| of the verification solve of the set-up (empty: cg path)
+  std::vector<double> cheb_lo, cheb_hi, cheb_achieved;
+  std::vector<int> cheb_its;
   int matmult(const double* x_dev, double* y_dev);      // MatMult(MATIS)
   int solve(const double* b_dev, double* x_dev, KspResult* res);  // KSPSolve counterpart
   int n_owned() const { return (int)owned.size(); }
+  int cheb_steps_per_solve() const { return cheb_K; }
+  void cheb_counters(long long* solves, long long* graph_launches, long long* fused_residuals) const {
+    *solves = cheb_solves;
+    *graph_launches = cheb_graph_launches;
+    *fused_residuals = cheb_res_fused;
+  }
+  std::vector<double> cheb_table() const;   // the device coefficient table, K x nsub x 2 (download)
   const double* x0_dev() const { return d_x0; }
   // results for parity tests
   std::vector<std::vector<double>> eigvals;      // per local subdomain: eigenvalues kept in Z
@@ -228,6 +262,24 @@ class PC {
   int cg_long_len = 0;         // length of the first chunk of a local solve once the first solve of this set-up is known (0: not yet, -1: never)
   bool cg_graph_failed = false;
   long long cg_chunks = 0;     // chunks issued so far (sampling of direct launches while the in-situ timer runs)
+  // Chebyshev local solver: coefficient table coef[(k ns + s) 2 + {0, 1}] = (a_k, b_k) of subdomain s (rows k >= k_s are
+  // zero), K = max_s k_s steps per solve, the direction vector, and the HIP graph of one whole solve
+  double* d_cheb_coef = nullptr;
+  int cheb_K = 0;
+  void* cheb_graph = nullptr;
+  double* cheb_graph_wL = nullptr;   // the graph names its buffers and the step kernel's form: recaptured when either changes
+  int cheb_graph_fused = -1;
+  bool cheb_graph_failed = false;
+  long long cheb_solves = 0;
+  // what ran (PCGenEOGetLocalSolverCounters): solves replayed from the graph, and residual updates r - A d that went
+  // through bk::cheb_residual (the others: bk::spmv and bk::axpy); cheb_graph_res is the latter's count inside the graph
+  long long cheb_graph_launches = 0, cheb_res_fused = 0;
+  int cheb_graph_res = 0;
+  ChebWork cheb_work;   // scratch of the composed step, sized by setup_cheb
+  int setup_cheb();
+  void cheb_release();
+  int cheb_steps(double* wL, const double* dscale);   // returns the number of residual updates bk::cheb_residual took
+  void local_solve_cheb(double* wL);
   HostCsr host_neu_cache, host_dir_cache;   // block-diagonal host copies of A_Neu / the level-1 matrix, reused by the next set-up
   AmgDevice* amg1 = nullptr;   // hierarchy of the level-1 (Dirichlet / Robin) block-diagonal matrix (local solves)
   AmgDevice* amgN = nullptr;   // hierarchy of the Neumann block-diagonal matrix (LOBPCG preconditioner)

@@ -101,8 +101,10 @@ class GenEOPC:
         out = {}
         for kv in self.lib.PCGenEOGetOptionsString(self.h).decode().split(";"):
             k, _, v = kv.partition("=")
-            if k in ("dls1_pc", "els2_pc", "ksp_type"):
+            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type"):
                 out[k] = v
+            elif k == "dls1_cheb_safety":
+                out[k] = tuple(float(t) for t in v.split(","))
             elif "." in v or "e" in v or "inf" in v:
                 out[k] = float(v)
             else:
@@ -290,6 +292,38 @@ class GenEOPC:
         v = [C.c_int(0) for _ in range(4)]
         self._chk(self.lib.PCGenEOGetCoarseInfo(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def local_solver_info(self):
+        """Chebyshev local solver (-dls1_ksp_type chebyshev), after the set-up: per local subdomain the bounds lo, hi of the
+        V-cycle-preconditioned operator, the degree k_s and the residual reduction of the set-up's verification solve
+        (PCGenEOGetLocalSolverInfo).  Four empty arrays on the cg path."""
+        n = self.lib.PCGenEOGetLocalSolverInfo(self.h, None, None, None, None, 0)
+        if n < 0:
+            raise GenEOError("PCGenEOGetLocalSolverInfo: bad handle")
+        lo, hi, ach = np.zeros(max(1, n)), np.zeros(max(1, n)), np.zeros(max(1, n))
+        its = np.zeros(max(1, n), dtype=np.int32)
+        self.lib.PCGenEOGetLocalSolverInfo(self.h, lo.ctypes.data_as(L.c_dbl_p), hi.ctypes.data_as(L.c_dbl_p),
+                                           its.ctypes.data_as(L.c_int_p), ach.ctypes.data_as(L.c_dbl_p), n)
+        return lo[:n], hi[:n], its[:n], ach[:n]
+
+    def local_solver_table(self):
+        """The Chebyshev coefficient table of the device, shape (K, nsub, 2): (a_k, b_k) per step and local subdomain."""
+        ns = self.lib.PCGenEOGetLocalSolverInfo(self.h, None, None, None, None, 0)
+        K = self.lib.PCGenEOGetLocalSolverTable(self.h, None, 0)
+        if K < 0 or ns < 0:
+            raise GenEOError(self.lib.PCGenEOGetError(self.h).decode())
+        t = np.zeros(max(1, K * ns * 2))
+        self.lib.PCGenEOGetLocalSolverTable(self.h, t.ctypes.data_as(L.c_dbl_p), K * ns * 2)
+        return t[:K * ns * 2].reshape(K, ns, 2)
+
+    def local_solver_counters(self):
+        """What the Chebyshev local solves ran since the last set-up (PCGenEOGetLocalSolverCounters): K steps per solve,
+        solves in all, solves replayed from the HIP graph, residual updates taken by the fused sliced kernel."""
+        v = [C.c_longlong(0) for _ in range(3)]
+        K = self.lib.PCGenEOGetLocalSolverCounters(self.h, *[C.byref(x) for x in v])
+        if K < 0:
+            raise GenEOError("PCGenEOGetLocalSolverCounters: bad handle")
+        return dict(K=K, solves=v[0].value, graph_launches=v[1].value, fused_residuals=v[2].value)
 
     def local_dims(self):
         n = self.lib.PCGenEOGetLocalDims(self.h, None, 0)

@@ -84,8 +84,17 @@ PetscErrorCode PCDestroy_GenEO(GENEO_PC* pc);
 /* ---- options (src/geneo.cpp:2329-2514) -------------------------------------------------- */
 /* Parses the -geneo_* options (same spellings, defaults, validation), plus the subset of the
  * forwarded prefixes this build understands: -els2_eps_{tol,nev,max_it,block,seed},
- * -els2_cheb_{degree,ratio}, -dls1_ksp_{rtol,max_it}, -ksp_{type,rtol,atol,divtol,max_it},
- * -ksp_gmres_restart.  Unknown options are ignored, like PETSc with -options_left no. */
+ * -els2_cheb_{degree,ratio}, -dls1_ksp_{type,rtol,max_it}, -ksp_{type,rtol,atol,divtol,max_it},
+ * -ksp_gmres_restart.  Unknown options are ignored, like PETSc with -options_left no.
+ * -dls1_ksp_type cg|chebyshev (default cg) chooses the Krylov method of the local solves: the batched V-cycle-PCG run to
+ * -dls1_ksp_rtol, or a fixed-degree Chebyshev iteration preconditioned by the same V-cycle (needs -dls1_pc_type amg; any
+ * other value is refused).  Chebyshev has no reductions and no host polling and is a fixed linear operator at any
+ * -dls1_ksp_rtol; per subdomain its bounds come from -dls1_cheb_esteig_its Lanczos steps (default 16) scaled by
+ * -dls1_cheb_safety lo,hi (default 0.9,1.1), and its degree is the smallest k with 1 / T_k(sigma) <= -dls1_ksp_rtol,
+ * at most -dls1_ksp_max_it.  With chebyshev both are read by the set-up, which fixes the degrees: changing them with
+ * PCGenEOSetOption afterwards has no effect before the next set-up (the cg path reads them at every solve).  A degree cut
+ * short by -dls1_ksp_max_it is no error here (the cg path raises KSP_DIVERGED_ITS): the operator stays linear, symmetric and
+ * positive definite, only less accurate, and PCGenEOGetLocalSolverInfo reports the degree and the reduction reached. */
 PetscErrorCode PCSetFromOptions_GenEO(GENEO_PC pc, int argc, const char* const* argv);
 PetscErrorCode PCGenEOSetOption(GENEO_PC pc, const char* key, const char* value);
 /* buildGenEOName, src/geneo.cpp:2245-2268 ("geneo1ASM", "geneo1HASM", ...) */
@@ -298,7 +307,9 @@ PetscErrorCode GeneoSetMFMA(int enable);         /* 0: run the plain-FMA twins o
 /* validation: choose between two device forms of the same arithmetic -- "spgemm_fill_scan" (1: owner-computes numeric pass
  * of the sparse products instead of the hash accumulators), "spgemm_small_rows" (0: rows of at most 64 products go through
  * the hash table as well), "gram_flat" (0: k_gram_mfma instead of k_gram_flat); both forms of each give bit-identical
- * results (tests/test_gpu_kernels.py).  Returns 1 for an unknown name. */
+ * results (tests/test_gpu_kernels.py).  "cheb_fused" (0: the step of the Chebyshev local solver composed of the plain
+ * vector primitives and its residual update as the plain product and a vector update, instead of their fused kernels;
+ * same bits).  Returns 1 for an unknown name. */
 PetscErrorCode GeneoSetKernelVariant(const char* name, int value);
 
 /* ---- stand-alone kernels (parity tests and the roofline leg of bench.py) --------------------- */
@@ -388,6 +399,22 @@ int GeneoTestPrimitive(const char* name, const int* iarg, const double* darg, vo
  * factorisation made the factor, 0 for the host's (Cholesky or LU).  solve_kind: 0 download / host sweeps / upload,
  * 1 the one-workgroup device sweeps (dimE <= 1024), 2 the blocked device sweeps.  block: their block size (0 unless 2). */
 PetscErrorCode PCGenEOGetCoarseInfo(PC pc, int* dimE, int* factor_on_device, int* solve_kind, int* block);
+/* ---- the Chebyshev local solver (-dls1_ksp_type chebyshev), after the set-up: per local subdomain (in the order they
+ * were added) the bounds [lo, hi] used for the V-cycle-preconditioned operator, the degree k_s, and ||b - A x|| / ||b|| of
+ * the set-up's verification solve.  Any array may be NULL; at most cap entries are written.  Returns the number of local
+ * subdomains, 0 on the cg path, -1 for a bad handle. */
+int PCGenEOGetLocalSolverInfo(PC pc, double* lo, double* hi, int* its, double* achieved, int cap);
+/* Its coefficient table as the device holds it: coef[(k nsub + s) 2 + {0, 1}] = (a_k, b_k) of local subdomain s, K = max k_s
+ * rows, rows k >= k_s of a subdomain exactly zero.  At most cap doubles are written (coef may be NULL); returns K (0 on the
+ * cg path), -1 on an error. */
+int PCGenEOGetLocalSolverTable(PC pc, double* coef, int cap);
+/* What its solves ran since the last set-up: *solves local solves in all, *graph_launches of them replayed from the
+ * captured HIP graph (the others went out as direct launches: the first solve, one in eight while the in-situ kernel
+ * timer runs, and every solve where capture is unavailable), and *fused_residuals residual updates r - A d taken by the
+ * fused sliced kernel (K - 1 per solve when the level-1 matrix is on the sliced path and "cheb_fused" is 1; the others
+ * ran the plain product and a vector update).  Any pointer may be NULL.  Returns K (0 on the cg path), -1 for a bad
+ * handle. */
+int PCGenEOGetLocalSolverCounters(PC pc, long long* solves, long long* graph_launches, long long* fused_residuals);
 /* Test hooks of the blocked kernels, HOST arrays (n x n row-major).  GeneoTestCoarseFactor: E = L L^T with block size nb;
  * L lower with a zero strict upper part, LT its transpose, *status 0 or 1 + the index of the first pivot that was not
  * positive.  GeneoTestCoarseSolve: y <- (L L^T)^-1 y, `reps` >= 1 times from the same y (timing).  Every device buffer of
