@@ -95,6 +95,10 @@ SYMBOLS = {
     "PCGenEOSetRHS": (C.c_int, [C.c_void_p, C.c_void_p]),
     "KSPSolve_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int_p, c_dbl_p, c_int_p]),
     "PCGenEOGetResidualHistory": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int]),
+    "PCMatApply_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "MatMatMult_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "KSPMatSolve_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_int_p, c_dbl_p, c_int_p]),
+    "PCGenEOGetBlockInfo": (C.c_int, [C.c_void_p, c_int_p] + [C.POINTER(C.c_longlong)] * 4),
     "PCGenEOGetInfo": (C.c_int, [C.c_void_p, C.POINTER(GeneoInfo)]),
     "PCGenEOGetEigenvalues": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
     "PCGenEOGetCandidates": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
@@ -163,6 +167,7 @@ SYMBOLS = {
     "GeneoBlockKernel": (C.c_int, [C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p,
                                    C.c_int, c_dbl_p]),
     "GeneoTestPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
+    "GeneoTestBlockPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
     "PCGenEOGetCoarseInfo": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p]),
     "PCGenEOGetLocalSolverInfo": (C.c_int, [C.c_void_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, C.c_int]),
     "PCGenEOGetLocalSolverTable": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int]),

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "../../include/geneo_c.h"
+#include "block_dev.h"
 #include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "core.h"
@@ -131,16 +132,17 @@ const char* PCGenEOGetName(PC pc) { return pc ? pc->name.c_str() : ""; }
 const char* PCGenEOGetOptionsString(PC pc) {
   if (!pc || !pc->ctx) return "";
   const geneo::Options& o = pc->ctx->opt;
-  char buf[1280];
+  char buf[1408];
   snprintf(buf, sizeof(buf),
            "lvl1ASM=%d;lvl1RAS=%d;lvl1SRAS=%d;lvl1ORAS=%d;lvl2=%d;hybrid=%d;effHybrid=%d;optim=%.17g;tau=%.17g;"
            "gamma=%.17g;cst=%d;cut=%d;noSyl=%d;offload=%d;eps_tol=%.17g;dls1_rtol=%.17g;dls1_pc=%s;els2_pc=%s;"
            "ksp_type=%s;ksp_rtol=%.17g;ksp_atol=%.17g;ksp_max_it=%d;ksp_restart=%d;"
-           "dls1_ksp_type=%s;dls1_cheb_esteig_its=%d;dls1_cheb_safety=%.17g,%.17g",
+           "dls1_ksp_type=%s;dls1_cheb_esteig_its=%d;dls1_cheb_safety=%.17g,%.17g;block_width=%d",
            (int)o.lvl1ASM, (int)o.lvl1RAS, (int)o.lvl1SRAS, (int)o.lvl1ORAS, o.lvl2, (int)o.hybrid, (int)o.effHybrid,
            o.optim, o.tau, o.gamma, (int)o.cst, o.cut, (int)o.noSyl, (int)o.offload, o.eps_tol, o.dls1_rtol,
            o.dls1_pc.c_str(), o.els2_pc.c_str(), o.ksp_type.c_str(), o.ksp_rtol, o.ksp_atol, o.ksp_max_it,
-           o.ksp_restart, o.dls1_ksp.c_str(), o.dls1_cheb_esteig_its, o.dls1_cheb_safety_lo, o.dls1_cheb_safety_hi);
+           o.ksp_restart, o.dls1_ksp.c_str(), o.dls1_cheb_esteig_its, o.dls1_cheb_safety_lo, o.dls1_cheb_safety_hi,
+           o.block_width);
   pc->optstr = buf;
   return pc->optstr.c_str();
 }
@@ -168,6 +170,10 @@ const char* usageGenEO_c(void) {
          "                   auto:   as never up to dimE 1024; above: blocked factorisation and sweeps on the GPU\n"
          "                   always: the blocked GPU kernels at any dimE (host sequence when E is not positive definite)\n"
          "  -geneo_coarse_block B   block size of the blocked kernels, a multiple of 16 in 16 .. 256 (defaults to 128)\n"
+         "  -geneo_block_width W   0 | 16 | 32 (defaults to 0): slab width of the block entry points PCMatApply_GenEO,\n"
+         "                   MatMatMult_GenEO and KSPMatSolve_GenEO (several right-hand sides per pass over the matrices); needs\n"
+         "                   -dls1_ksp_type chebyshev; read by the set-up, a later change waits for the next set-up; 0 allocates\n"
+         "                   and builds nothing\n"
          "  -geneo_nicolaides_zero X   the Nicolaides rule takes min(lambda) >= X eps as 'no zero eigenvalue found'\n"
          "                   (1 = the reference's literal test; defaults to 100)\n"
          "  -geneo_eig_group_rows R / -geneo_eig_mem_gb G   memory-bounded set-up: eigensolve the rank's subdomains in\n"
@@ -353,6 +359,30 @@ PetscErrorCode KSPSolve_GenEO(PC pc, const double* b, double* x, int* its, doubl
   if (reason) *reason = r.reason;
   return propagate(pc, rc);
   GUARD_END(pc)
+}
+PetscErrorCode PCMatApply_GenEO(PC pc, const double* X, int ldx, double* Y, int ldy, int m) {
+  if (!pc || !pc->ctx) return 1;
+  GUARD_BEGIN
+  return propagate(pc, pc->ctx->apply_mat(X, ldx, Y, ldy, m));
+  GUARD_END(pc)
+}
+PetscErrorCode MatMatMult_GenEO(PC pc, const double* X, int ldx, double* Y, int ldy, int m) {
+  if (!pc || !pc->ctx) return 1;
+  GUARD_BEGIN
+  return propagate(pc, pc->ctx->matmult_mat(X, ldx, Y, ldy, m));
+  GUARD_END(pc)
+}
+PetscErrorCode KSPMatSolve_GenEO(PC pc, const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm,
+                                 int* reason) {
+  if (!pc || !pc->ctx) return 1;
+  GUARD_BEGIN
+  return propagate(pc, pc->ctx->solve_mat(B, ldb, X, ldx, m, its, rnorm, reason));
+  GUARD_END(pc)
+}
+int PCGenEOGetBlockInfo(PC pc, int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) {
+  if (!pc || !pc->ctx) return -1;
+  pc->ctx->block_info(width, slabs, columns, padded, graph_launches);
+  return 0;
 }
 int PCGenEOGetResidualHistory(PC pc, double* hist, int cap) {
   if (!pc || !pc->ctx) return 0;
@@ -586,6 +616,10 @@ PetscErrorCode GeneoSetMFMA(int enable) {
 PetscErrorCode GeneoSetKernelVariant(const char* name, int value) {
   if (name && std::string(name) == "cheb_fused") {     // a choice of core.cpp, not of the backend: bk::cheb_dir / bk::cheb_residual or their composed forms
     geneo::set_cheb_fused(value);
+    return 0;
+  }
+  if (name && std::string(name) == "block_fused") {    // likewise: the kernels of block_dev.h or their composed forms
+    geneo::set_block_fused(value);
     return 0;
   }
   return bk::set_variant(name, value) ? 0 : 1;
@@ -933,6 +967,64 @@ int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* co
       else if (k == "zt_apply") bk::zt_apply(c, d(1), lp(2), ip(3), ip(4), I[1], d(5), d(6), I[2]);
       else if (k == "z_apply") bk::z_apply(c, d(1), lp(2), ip(3), ip(4), d(5), d(6), I[1] != 0);
       else rc = -2;
+    }
+    bk::sync();
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    rc = -1;
+  }
+  if (have_chunks) bk::chunks_free(c);
+  return rc;
+}
+
+// ---- test hook of the block primitives (block_dev.h; argument table: tests/block_rhs_util.py) ---------------------------
+// As GeneoTestPrimitive: unpack, call, leave the results where the primitive wrote them.  "block_fused" 0 runs the composed
+// forms of core.cpp instead.  Returns 0 / 1 (the primitive's bool), -1 on an exception, -2 for an unknown name.
+int GeneoTestBlockPrimitive(const char* name, const int* I, const double* D, void* const* P) {
+  (void)D;
+  const std::string k(name ? name : "");
+  auto d = [&](int i) { return (double*)P[i]; };
+  const bool fused = geneo::block_fused() != 0;
+  bk::Chunks c;
+  bool have_chunks = false;
+  int rc = 0;
+  try {
+    if (k == "cheb_dir_block") {
+      c = bk::chunks_upload(I[0], (const int*)P[0]);
+      have_chunks = true;
+      rc = (fused ? bk::cheb_dir_block(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), I[2])
+                  : geneo::cheb_dir_block_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), I[2])) ? 1 : 0;
+    } else if (k == "block_import") {
+      rc = (fused ? bk::block_import(d(0), I[0], I[1], I[2], d(1), I[3])
+                  : geneo::block_import_composed(d(0), I[0], I[1], I[2], d(1), I[3])) ? 1 : 0;
+    } else if (k == "block_export") {
+      rc = (fused ? bk::block_export(d(0), I[3], I[1], I[2], d(1), I[0])
+                  : geneo::block_export_composed(d(0), I[3], I[1], I[2], d(1), I[0])) ? 1 : 0;
+    } else if (k == "block_coldot") {
+      if (fused) {
+        double* work = (double*)bk::alloc(sizeof(double) * (size_t)bk::BLOCK_COLDOT_WG * I[1]);
+        try {
+          rc = bk::block_coldot(d(0), d(1), I[0], I[1], d(2), work) ? 1 : 0;
+          bk::sync();
+        } catch (...) {
+          bk::dfree(work);
+          throw;
+        }
+        bk::dfree(work);
+      } else {
+        rc = geneo::block_coldot_composed_once(d(0), d(1), I[0], I[1], d(2)) ? 1 : 0;
+      }
+    } else if (k == "block_axpy_cols") {
+      rc = (fused ? bk::block_axpy_cols(d(0), d(1), d(2), I[0], I[1])
+                  : geneo::block_axpy_cols_composed_once(d(0), d(1), d(2), I[0], I[1])) ? 1 : 0;
+    } else if (k == "block_xpby_cols") {
+      rc = (fused ? bk::block_xpby_cols(d(0), d(1), d(2), I[0], I[1])
+                  : geneo::block_xpby_cols_composed_once(d(0), d(1), d(2), I[0], I[1])) ? 1 : 0;
+    } else if (k == "chol_solve_block") {
+      rc = (fused ? bk::chol_solve_block(d(0), d(1), I[0], d(2), I[1])
+                  : geneo::chol_solve_block_composed_once(d(0), d(1), I[0], d(2), I[1])) ? 1 : 0;
+    } else {
+      rc = -2;
     }
     bk::sync();
   } catch (std::exception& e) {

@@ -35,6 +35,7 @@
 #include <thread>
 
 #include "amg.h"
+#include "block_dev.h"
 #include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "dense.h"
@@ -126,6 +127,188 @@ __attribute__((weak)) bool cheb_dir(const Chunks& c, const double* coef_k, int f
   return geneo::cheb_dir_composed_once(c, coef_k, flags, z, d, x, dscale, out);
 }
 __attribute__((weak)) bool cheb_residual(const Csr&, const double*, const double*, double*) { return false; }
+}  // namespace bk
+
+// The operations of the block entry points (block_dev.h) composed of backend.h primitives: what a backend without
+// block_dev.hip links (the host twin), and on the GPU the comparison GeneoSetKernelVariant("block_fused", 0) selects.
+// Products and sums are rounded one by one, as the kernels do: block_colscale stores the rounded product, axpy with factor
+// 1 adds with one rounding; copies of columns go through block_axpby(.., 1, .., 0, ..), which moves bits.
+namespace geneo {
+static std::atomic<int> g_block_fused{1};
+void set_block_fused(int on) { g_block_fused = on ? 1 : 0; }
+int block_fused() { return g_block_fused.load(); }
+
+static int slab_entries(int n, int w) {
+  if ((int64_t)n * w > 0x7fffffffll) throw std::runtime_error("GenEO: a slab of right-hand sides exceeds 2^31 entries");
+  return n * w;
+}
+
+void BlockWork::alloc(int n_, int ns_, int w_) {
+  release();
+  if (n_ <= 0 || ns_ <= 0 || w_ <= 0) return;
+  t = (double*)bk::alloc(sizeof(double) * (size_t)n_ * w_);
+  ab = (double*)bk::alloc(sizeof(double) * 2 * (size_t)ns_ * w_);
+  idx = (int*)bk::alloc(sizeof(int) * 2 * (size_t)ns_ * w_);
+  std::vector<int> h(2 * (size_t)ns_ * w_);
+  for (int s = 0; s < ns_; ++s)
+    for (int j = 0; j < w_; ++j) {
+      h[(size_t)s * w_ + j] = 2 * s;                           // a_s on every column ...
+      h[(size_t)ns_ * w_ + (size_t)s * w_ + j] = 2 * s + 1;    // ... then b_s
+    }
+  bk::h2d(idx, h.data(), sizeof(int) * h.size());
+  n = n_;
+  ns = ns_;
+  w = w_;
+}
+void BlockWork::release() {
+  bk::dfree(t);
+  bk::dfree(ab);
+  bk::dfree(idx);
+  t = ab = nullptr;
+  idx = nullptr;
+  n = ns = w = 0;
+}
+
+bool cheb_dir_block_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                             const double* dscale, double* Out, int w, const BlockWork& wk) {
+  const int n = c.n, ns = c.nsub;
+  if (n <= 0 || ns <= 0) return true;
+  if (wk.n < n || wk.ns != ns || wk.w != w) throw std::runtime_error("cheb_dir_block_composed: scratch of another size");
+  const int nw = slab_entries(n, w);
+  bk::gather(wk.ab, coef_k, wk.idx, 2 * ns * w);
+  if (flags & 1) {
+    bk::copy(D, Z, nw);
+    bk::block_colscale(c, D, w, w, wk.ab);
+    bk::copy(X, D, nw);
+  } else {
+    bk::copy(wk.t, Z, nw);
+    bk::block_colscale(c, wk.t, w, w, wk.ab);
+    bk::block_colscale(c, D, w, w, wk.ab + (size_t)ns * w);
+    bk::axpy(D, 1.0, wk.t, nw);
+    bk::axpy(X, 1.0, D, nw);
+  }
+  if (flags & 2) {
+    if (dscale) bk::block_rowscale(Out, w, X, w, dscale, 1.0, 0.0, n, w);
+    else bk::copy(Out, X, nw);
+  }
+  return true;
+}
+
+bool cheb_dir_block_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                                  const double* dscale, double* Out, int w) {
+  struct Own {
+    BlockWork w;
+    ~Own() { w.release(); }
+  } own;
+  own.w.alloc(c.n, c.nsub, w);
+  const bool ok = cheb_dir_block_composed(c, coef_k, flags, Z, D, X, dscale, Out, w, own.w);
+  bk::sync();
+  return ok;
+}
+
+bool block_import_composed(const double* Xcm, int ld, int n, int m, double* Yrm, int w) {
+  if (n <= 0) return true;
+  bk::zero(Yrm, sizeof(double) * (size_t)n * w);
+  for (int j = 0; j < m; ++j) bk::block_axpby(Yrm + j, w, 1.0, Xcm + (size_t)j * ld, 1, 0.0, n, 1);
+  return true;
+}
+bool block_export_composed(const double* Xrm, int w, int n, int m, double* Ycm, int ld) {
+  for (int j = 0; j < m; ++j) bk::block_axpby(Ycm + (size_t)j * ld, 1, 1.0, Xrm + j, w, 0.0, n, 1);
+  return true;
+}
+
+namespace {
+struct OnceBufs {     // scratch of a _once form: freed on every way out
+  std::vector<void*> v;
+  bk::Chunks c1;
+  double* get(size_t n) {
+    v.push_back(bk::alloc(sizeof(double) * std::max<size_t>(1, n)));
+    return (double*)v.back();
+  }
+  const bk::Chunks& rows(int n) {     // the n rows as ONE subdomain: block_colscale then scales whole columns
+    const int off[2] = {0, n};
+    c1 = bk::chunks_upload(1, off);
+    return c1;
+  }
+  ~OnceBufs() {
+    for (void* p : v) bk::dfree(p);
+    if (c1.start) bk::chunks_free(c1);
+  }
+};
+}  // namespace
+
+bool block_coldot_composed_once(const double* X, const double* Y, int n, int w, double* out) {
+  bk::zero(out, sizeof(double) * w);
+  if (n <= 0) return true;
+  OnceBufs b;
+  double *t = b.get(n), *u = b.get(n);
+  for (int j = 0; j < w; ++j) {
+    bk::block_axpby(t, 1, 1.0, X + j, w, 0.0, n, 1);
+    bk::block_axpby(u, 1, 1.0, Y + j, w, 0.0, n, 1);
+    bk::dot(t, u, n, out + j);
+  }
+  bk::sync();
+  return true;
+}
+bool block_axpy_cols_composed_once(double* Y, const double* X, const double* c, int n, int w) {
+  if (n <= 0) return true;
+  const int nw = slab_entries(n, w);
+  OnceBufs b;
+  double* t = b.get(nw);
+  bk::copy(t, X, nw);
+  bk::block_colscale(b.rows(n), t, w, w, c);
+  bk::axpy(Y, 1.0, t, nw);
+  bk::sync();
+  return true;
+}
+bool block_xpby_cols_composed_once(double* P, const double* Z, const double* c, int n, int w) {
+  if (n <= 0) return true;
+  const int nw = slab_entries(n, w);
+  OnceBufs b;
+  bk::block_colscale(b.rows(n), P, w, w, c);
+  bk::axpy(P, 1.0, Z, nw);
+  bk::sync();
+  return true;
+}
+bool chol_solve_block_composed_once(const double* L, const double* LT, int n, double* Y, int w) {
+  if (n <= 0) return true;
+  if (n > 1024) return false;
+  OnceBufs b;
+  double* t = b.get(n);
+  bool ok = true;
+  for (int j = 0; j < w && ok; ++j) {
+    bk::block_axpby(t, 1, 1.0, Y + j, w, 0.0, n, 1);
+    ok = bk::chol_solve(L, LT, n, t);
+    if (ok) bk::block_axpby(Y + j, w, 1.0, t, 1, 0.0, n, 1);
+  }
+  bk::sync();
+  return ok;
+}
+}  // namespace geneo
+
+namespace bk {
+__attribute__((weak)) bool cheb_dir_block(const Chunks& c, const double* coef_k, int flags, const double* Z, double* D,
+                                          double* X, const double* dscale, double* Out, int w) {
+  return geneo::cheb_dir_block_composed_once(c, coef_k, flags, Z, D, X, dscale, Out, w);
+}
+__attribute__((weak)) bool block_import(const double* Xcm, int ld, int n, int m, double* Yrm, int w) {
+  return geneo::block_import_composed(Xcm, ld, n, m, Yrm, w);
+}
+__attribute__((weak)) bool block_export(const double* Xrm, int w, int n, int m, double* Ycm, int ld) {
+  return geneo::block_export_composed(Xrm, w, n, m, Ycm, ld);
+}
+__attribute__((weak)) bool block_coldot(const double* X, const double* Y, int n, int w, double* out, double*) {
+  return geneo::block_coldot_composed_once(X, Y, n, w, out);
+}
+__attribute__((weak)) bool block_axpy_cols(double* Y, const double* X, const double* c, int n, int w) {
+  return geneo::block_axpy_cols_composed_once(Y, X, c, n, w);
+}
+__attribute__((weak)) bool block_xpby_cols(double* P, const double* Z, const double* c, int n, int w) {
+  return geneo::block_xpby_cols_composed_once(P, Z, c, n, w);
+}
+__attribute__((weak)) bool chol_solve_block(const double* L, const double* LT, int n, double* Y, int w) {
+  return geneo::chol_solve_block_composed_once(L, LT, n, Y, w);
+}
 }  // namespace bk
 
 namespace geneo {
@@ -272,6 +455,13 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
     o.els2_pc = value;
     return "";
   }
+  if (key == "-geneo_block_width") {
+    int v;
+    if (!to_int(value, v) || (v != 0 && v != 16 && v != 32))
+      return "invalid option -geneo_block_width, " + value + " is not 0, 16 or 32";
+    o.block_width = v;
+    return "";
+  }
   if (key == "-dls1_amg_strength") return dbl(o.dls1_amg_strength);
   if (key == "-els2_amg_strength") return dbl(o.els2_amg_strength);
   if (key == "-dls1_amg_precision") {
@@ -371,6 +561,7 @@ void PC::free_all() {
   cg_graph_failed = false;
   cg_long_len = 0;
   cheb_release();
+  block_release();
   delete amg1;
   delete amgN;
   amg1 = amgN = nullptr;
@@ -859,6 +1050,15 @@ int PC::setup_prepare() {
   const auto t_rel = clk::now();
   free_all();
   release_secs = secs(t_rel, clk::now());
+  if (opt.block_width > 0 && !eig_only) {     // the block entry points: what they need is known before anything is built
+    if (opt.dls1_ksp != "chebyshev")
+      return fail("GenEO preconditioner: -geneo_block_width " + std::to_string(opt.block_width) +
+                  " needs -dls1_ksp_type chebyshev (-dls1_ksp_type " + opt.dls1_ksp + " has no block form)");
+    if (size > 1 && comm_width < opt.block_width)
+      return fail("GenEO preconditioner: -geneo_block_width " + std::to_string(opt.block_width) +
+                  " needs halo buffers of that many vectors per exchange (PCGenEOSetCommWidth / the RCCL plan's max_width is " +
+                  std::to_string(comm_width) + ")");
+  }
   if (getenv("GENEO_DEBUG")) fprintf(stderr, "[setup] release of the previous set-up (outside setupTime) %.4f s\n", release_secs);
   info = Info();
   if (!eig_only) (void)amg_null_pivots_take();     // (a group of eigen_grouped counts into its owner's total)
@@ -1058,7 +1258,7 @@ int PC::setup_prepare() {
     lap("diagonals");
     auto ta = clk::now();
     // GenEO-2 runs the gamma eigenproblem through this hierarchy with whole blocks
-    const int max_m1 = (opt.lvl2 == 2 && opt.els2_pc == "amg") ? eig_block_max() : 1;
+    const int max_m1 = std::max((opt.lvl2 == 2 && opt.els2_pc == "amg") ? eig_block_max() : 1, eig_only ? 0 : opt.block_width);
     auto start1 = [this, ap1h, max_m1]() {
       Amg1Pending* pp = pend1.get();
       const std::vector<int> so = suboff;
@@ -1164,6 +1364,19 @@ int PC::setup_finish(const double* b_dev) {
   }
   if (opt.lvl2) {
     if (int rc = setup_level2(b_dev)) {
+      is_setup = false;
+      return rc;
+    }
+  }
+  if (opt.block_width > 0 && !eig_only) {     // work space, row-major Z and index maps of the block entry points
+    int rc = 1;
+    try {
+      rc = setup_block();
+    } catch (std::exception& e) {
+      rc = fail(e.what());
+    }
+    if (rc) {
+      block_release();
       is_setup = false;
       return rc;
     }
@@ -1648,6 +1861,18 @@ void PC::local_solve_cheb(double* wL) {
   info.dls1_solves += 1;
 }
 
+// yE <- E^-1 yE by the path of the factor this set-up made (see coarse_solve_local)
+void PC::coarse_einv(double* yE) {
+  if (E_dev) {
+    if (!bk::coarse_solve(d_EL, d_ELT, dimE, E_nb, yE)) throw std::runtime_error("GenEO - solve KO: dcs2 (no blocked coarse sweeps on this backend)");
+  } else if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
+    bk::d2h(h_yE.data(), yE, sizeof(double) * dimE);
+    if (E_chol) dense::cholesky_solve_lu(Efac, EfacT, dimE, h_yE.data());
+    else dense::lu_solve(Efac, dimE, Epiv, h_yE.data());
+    bk::h2d(yE, h_yE.data(), sizeof(double) * dimE);
+  }
+}
+
 // yE = E^-1 Z^T x, Z^T x taken from the already restricted xL; replicated host solve
 void PC::coarse_solve_local(const double* xL, double* yE) {
   auto t0 = clk::now();
@@ -1658,14 +1883,7 @@ void PC::coarse_solve_local(const double* xL, double* yE) {
   // sweeps are one launch behind the all-reduce -- no download, host solve, upload and no host synchronisation in the
   // preconditioner application.  A factor made on the device (build_E) takes the blocked sweeps, at any dimE, stream-ordered
   // in the same way.  Host path: E not positive definite to rounding (LU with pivoting), or dimE > 1024 with a host factor.
-  if (E_dev) {
-    if (!bk::coarse_solve(d_EL, d_ELT, dimE, E_nb, yE)) throw std::runtime_error("GenEO - solve KO: dcs2 (no blocked coarse sweeps on this backend)");
-  } else if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
-    bk::d2h(h_yE.data(), yE, sizeof(double) * dimE);
-    if (E_chol) dense::cholesky_solve_lu(Efac, EfacT, dimE, h_yE.data());
-    else dense::lu_solve(Efac, dimE, Epiv, h_yE.data());
-    bk::h2d(yE, h_yE.data(), sizeof(double) * dimE);
-  }
+  coarse_einv(yE);
   auto t2 = clk::now();
   info.lvl2ApplyZtTimeLoc += secs(t0, t1);
   info.lvl2ApplyEinvTimeLoc += secs(t1, t2);
@@ -1730,6 +1948,287 @@ int PC::apply(const double* x, double* y) {
     if (have_q) bk::axpy(y, 1.0, w, nown);
     else bk::copy(y, w, nown);
     info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+  } catch (std::exception& e) {
+    return fail(e.what());
+  }
+  return 0;
+}
+
+// ---- blocks of right-hand sides (-geneo_block_width 16 | 32; PCMatApply_GenEO, MatMatMult_GenEO, KSPMatSolve_GenEO) ----
+// Slabs of w columns, row-major, through the block forms of the restriction, the prolongation and the operator that the
+// assembly of E uses, the V-cycle on blocks that LOBPCG uses, and the kernels of block_dev.h.  With the Chebyshev local
+// solver the local solve is the same fixed linear operator for every column: its chain of launches with SpMM in place of
+// SpMV.  The block V-cycle reads the FP64 level matrices; under -dls1_amg_precision single the single-vector path reads
+// their float companions, so the two are then slightly different (fixed, linear, symmetric) operators.
+void PC::block_release() {
+  if (blk_graph) bk::graph_destroy(blk_graph);
+  blk_graph = nullptr;
+  blk_graph_fused = -1;
+  blk_graph_failed = false;
+  void* ptrs[] = {blk_r0, blk_r1, blk_z, blk_d, blk_x, blk_in, blk_out, blk_t1, blk_t2, blk_t3, blk_xe, blk_yE, blk_G,
+                  blk_C, blk_ZR, blk_col, blk_dots, blk_dotwork, blk_coef, blk_g2e, blk_e2c};
+  for (void* p : ptrs) bk::dfree(p);
+  blk_r0 = blk_r1 = blk_z = blk_d = blk_x = blk_in = blk_out = blk_t1 = blk_t2 = blk_t3 = blk_xe = nullptr;
+  blk_yE = blk_G = blk_C = blk_ZR = blk_col = blk_dots = blk_dotwork = blk_coef = nullptr;
+  blk_g2e = blk_e2c = nullptr;
+  blk_work.release();
+  blk_w = blk_kp = 0;
+  blk_slabs = blk_columns = blk_padded = blk_graph_launches = blk_solves = 0;
+}
+
+// Work space of the block entry points, allocated once per set-up (released by the next set-up and by destroy).
+int PC::setup_block() {
+  block_release();
+  const int w = opt.block_width;
+  if (w == 0) return 0;
+  if (opt.dls1_ksp != "chebyshev" || !amg1) return fail("GenEO preconditioner: -geneo_block_width needs -dls1_ksp_type chebyshev");
+  const int ns = (int)subs.size(), nown = n_owned();
+  slab_entries(std::max(nL, std::max(nE, nown)), w);
+  auto dv = [](size_t n) { return (double*)bk::alloc(sizeof(double) * std::max<size_t>(1, n)); };
+  for (double** p : {&blk_r0, &blk_r1, &blk_z, &blk_d, &blk_x}) *p = dv((size_t)nL * w);
+  for (double** p : {&blk_in, &blk_out, &blk_t1, &blk_t2, &blk_t3}) *p = dv((size_t)nown * w);
+  blk_xe = dv((size_t)std::max(nE, nown) * w);
+  blk_dots = dv(w);
+  blk_coef = dv(2 * (size_t)w);
+  blk_dotwork = dv((size_t)bk::BLOCK_COLDOT_WG * w);
+  if (opt.lvl2 && dimE > 0 && d_Z) {
+    // Z row-major, as build_E makes it; Gram rows <-> rows of the replicated coarse block <-> coefficient rows of the
+    // block update are row gathers.  Each source carries one extra row that stays zero: coarse rows of other ranks'
+    // subdomains, and the coefficient rows k >= k_s of a subdomain.
+    const int kp = ((std::max(1, kmax) + 15) / 16) * 16;
+    blk_kp = kp;
+    blk_ZR = dv((size_t)nL * kp);
+    bk::z_rowmajor(ch, d_Z, d_zbase, d_ksub, blk_ZR, kp);
+    blk_yE = dv(((size_t)dimE + 1) * w);
+    blk_G = dv(((size_t)ns * kp + 1) * w);
+    blk_C = dv((size_t)std::max(1, ns) * kp * w);
+    blk_col = dv(dimE);
+    bk::zero(blk_yE + (size_t)dimE * w, sizeof(double) * w);
+    bk::zero(blk_G + (size_t)ns * kp * w, sizeof(double) * w);
+    std::vector<int> g2e(dimE, ns * kp), e2c((size_t)std::max(1, ns) * kp, dimE);
+    for (int s = 0; s < ns; ++s)
+      for (int k = 0; k < ksub[s]; ++k) {
+        g2e[zoff[s] + k] = s * kp + k;
+        e2c[(size_t)s * kp + k] = zoff[s] + k;
+      }
+    blk_g2e = (int*)bk::alloc(sizeof(int) * g2e.size());
+    blk_e2c = (int*)bk::alloc(sizeof(int) * e2c.size());
+    bk::h2d(blk_g2e, g2e.data(), sizeof(int) * g2e.size());
+    bk::h2d(blk_e2c, e2c.data(), sizeof(int) * e2c.size());
+  }
+  blk_w = w;
+  return 0;
+}
+
+void PC::block_info(int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) const {
+  if (width) *width = blk_w;
+  if (slabs) *slabs = blk_slabs;
+  if (columns) *columns = blk_columns;
+  if (padded) *padded = blk_padded;
+  if (graph_launches) *graph_launches = blk_graph_launches;
+}
+
+// The K steps on the slab blk_r0 (the graph names its buffers, so the slab is fixed): WL holds the right-hand sides on entry and the solutions (dscale .* them) on return.  The
+// residual travels between WL and blk_r1 (out of place through the fused residual epilogue of the SpMM).
+void PC::block_steps(const double* dscale) {
+  double* const WL = blk_r0;
+  const int ns = (int)subs.size(), K = cheb_K, w = blk_w;
+  const bool fused = g_block_fused.load() != 0;
+  double *rc = WL, *ro = blk_r1;
+  for (int k = 0; k < K; ++k) {
+    amg1->vcycle(rc, w, blk_z, w, w);
+    const int flags = (k == 0 ? 1 : 0) | (k == K - 1 ? 2 : 0);
+    const double* ck = d_cheb_coef + (size_t)k * ns * 2;
+    if (fused) bk::cheb_dir_block(ch, ck, flags, blk_z, blk_d, blk_x, dscale, WL, w);
+    else cheb_dir_block_composed(ch, ck, flags, blk_z, blk_d, blk_x, dscale, WL, w, blk_work);
+    if (k == K - 1) break;
+    bk::spmm_fused(dirL, bk::EPI_RES, blk_d, w, ro, w, w, rc, w, nullptr, 0, nullptr, 0.0);   // r_out = r_in - A d
+    std::swap(rc, ro);
+  }
+}
+
+// [D] M^-1 [D] on a slab: local_solve_cheb with block kernels.  One linear chain on one stream, captured once per set-up
+// into a HIP graph of its own: the first slab goes out directly (the graph is recorded next to it), later ones replay, one
+// in eight goes direct while the in-situ kernel timer runs.
+void PC::local_solve_block() {
+  double* const WL = blk_r0;
+  if (nL == 0 || subs.empty()) return;
+  if (!d_cheb_coef || cheb_K <= 0 || !amg1) throw std::runtime_error("GenEO - solve KO: dls1 (-dls1_ksp_type chebyshev was not set up)");
+  const int w = blk_w;
+  if (opt.lvl1RAS) bk::block_rowscale(WL, w, WL, w, d_D, 1.0, 0.0, nL, w);
+  const double* dscale = opt.lvl1SRAS ? d_D : nullptr;
+  const int fused = g_block_fused.load();
+  if (!fused && !blk_work.t) blk_work.alloc(nL, (int)subs.size(), w);     // (before any capture: nothing is allocated inside one)
+  if (blk_graph && blk_graph_fused != fused) {
+    bk::graph_destroy(blk_graph);
+    blk_graph = nullptr;
+  }
+  bool direct = false;
+  if (!blk_graph) {
+    direct = true;
+    if (!blk_graph_failed && bk::graph_capture_begin()) {
+      try {
+        block_steps(dscale);
+      } catch (...) {
+        bk::graph_capture_end();
+        blk_graph_failed = true;
+        throw;
+      }
+      blk_graph = bk::graph_capture_end();
+      blk_graph_fused = fused;
+      if (!blk_graph) blk_graph_failed = true;
+    } else {
+      blk_graph_failed = true;
+    }
+  } else if (bk::spmv_profiling() && (blk_solves % 8 == 0)) {
+    direct = true;
+  }
+  ++blk_solves;
+  if (direct) {
+    block_steps(dscale);
+  } else {
+    bk::graph_launch(blk_graph);
+    ++blk_graph_launches;
+  }
+  info.dls1_iterations += cheb_K;     // one chain of K steps, whatever the width
+  info.dls1_solves += 1;
+}
+
+// YE <- E^-1 YE on the dimE x w block.  A host-made Cholesky factor on the device (dimE <= 1024): one launch for all
+// columns.  A factor made on the device, or one the host alone holds: column by column through the single-vector path.
+void PC::coarse_einv_block(double* YE) {
+  const int w = blk_w;
+  if (!E_dev && E_chol && d_EL && dimE <= 1024) {
+    const bool ok = g_block_fused.load() ? bk::chol_solve_block(d_EL, d_ELT, dimE, YE, w)
+                                         : chol_solve_block_composed_once(d_EL, d_ELT, dimE, YE, w);
+    if (ok) return;
+  }
+  for (int j = 0; j < w; ++j) {
+    bk::block_axpby(blk_col, 1, 1.0, YE + j, w, 0.0, dimE, 1);
+    coarse_einv(blk_col);
+    bk::block_axpby(YE + j, w, 1.0, blk_col, 1, 0.0, dimE, 1);
+  }
+}
+
+// blk_C[s] (kp x w) = the rows of E^-1 Z^T X that belong to subdomain s, Z^T X taken from the restricted slab XL
+void PC::coarse_solve_block(const double* XL) {
+  const int w = blk_w, kp = blk_kp, ns = (int)subs.size();
+  auto t0 = clk::now();
+  bk::gram(ch, blk_ZR, kp, kp, XL, w, w, blk_G);
+  bk::gather_rows(blk_yE, blk_G, blk_g2e, dimE, w);
+  allreduce(blk_yE, slab_entries(dimE, w));
+  auto t1 = clk::now();
+  coarse_einv_block(blk_yE);
+  bk::gather_rows(blk_C, blk_yE, blk_e2c, ns * kp, w);
+  info.lvl2ApplyZtTimeLoc += secs(t0, t1);
+  info.lvl2ApplyEinvTimeLoc += secs(t1, clk::now());
+}
+
+void PC::apply_q_block(const double* X, double* Y) {
+  const int w = blk_w;
+  if (!blk_ZR) {       // an empty coarse space: Q = 0
+    bk::zero(Y, sizeof(double) * (size_t)n_owned() * w);
+    return;
+  }
+  restrict_block(X, blk_x, w, blk_xe);
+  coarse_solve_block(blk_x);
+  bk::block_mul(ch, blk_ZR, blk_kp, blk_kp, blk_C, w, blk_r0, w, false);
+  prolong_block(blk_r0, Y, w, blk_xe);
+}
+
+// PC::apply on an owned slab, branch for branch
+void PC::apply_block(const double* X, double* Y) {
+  const int w = blk_w, nw = slab_entries(n_owned(), w);
+  auto t0 = clk::now();
+  if (opt.lvl2 && !opt.hybrid) {
+    restrict_block(X, blk_r0, w, blk_xe);
+    if (blk_ZR) coarse_solve_block(blk_r0);
+    auto t1 = clk::now();
+    local_solve_block();
+    auto t2 = clk::now();
+    if (blk_ZR) bk::block_mul(ch, blk_ZR, blk_kp, blk_kp, blk_C, w, blk_r0, w, true);
+    prolong_block(blk_r0, Y, w, blk_xe);
+    info.lvl2ApplyTimeLoc += secs(t0, t1);
+    info.lvl1ApplyMinvTimeLoc += secs(t1, t2);
+    info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+    return;
+  }
+  bool have_q = false;
+  if (opt.lvl2 && !opt.effHybrid) {
+    apply_q_block(X, Y);
+    have_q = true;
+    info.lvl2ApplyTimeLoc += secs(t0, clk::now());
+  }
+  auto t1 = clk::now();
+  double* W = blk_t1;
+  bk::copy(W, X, nw);
+  if (opt.hybrid && !opt.effHybrid) {  // (I - P^T)
+    matmult_block(Y, blk_t2, w, blk_r0, blk_xe);
+    bk::axpy(W, -1.0, blk_t2, nw);
+  }
+  restrict_block(W, blk_r0, w, blk_xe);
+  auto t2 = clk::now();
+  local_solve_block();
+  info.lvl1ApplyMinvTimeLoc += secs(t2, clk::now());
+  prolong_block(blk_r0, W, w, blk_xe);
+  if (opt.hybrid) {  // (I - P)
+    matmult_block(W, blk_t2, w, blk_r0, blk_xe);
+    apply_q_block(blk_t2, blk_t3);
+    bk::axpy(W, -1.0, blk_t3, nw);
+  }
+  if (have_q) bk::axpy(Y, 1.0, W, nw);
+  else bk::copy(Y, W, nw);
+  info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+}
+
+int PC::block_check(const char* who, int ld, int m, const void* a, const void* b) {
+  if (!is_setup) return fail(std::string(who) + ": GenEO preconditioner is not set up");
+  if (blk_w == 0) return fail(std::string(who) + ": the preconditioner was set up without -geneo_block_width (16 or 32)");
+  if (m < 1) return fail(std::string(who) + ": the block needs at least one column");
+  if (ld < n_owned()) return fail(std::string(who) + ": leading dimension " + std::to_string(ld) + " is below the " +
+                                  std::to_string(n_owned()) + " owned rows");
+  if (!a || !b) return fail(std::string(who) + ": null block");
+  return 0;
+}
+
+void PC::slab_in(const double* Xcm, int ld, int m, double* slab) {
+  if (g_block_fused.load()) bk::block_import(Xcm, ld, n_owned(), m, slab, blk_w);
+  else block_import_composed(Xcm, ld, n_owned(), m, slab, blk_w);
+}
+void PC::slab_out(const double* slab, int m, double* Ycm, int ld) {
+  if (g_block_fused.load()) bk::block_export(slab, blk_w, n_owned(), m, Ycm, ld);
+  else block_export_composed(slab, blk_w, n_owned(), m, Ycm, ld);
+}
+
+int PC::apply_mat(const double* X, int ldx, double* Y, int ldy, int m) {
+  if (int rc = block_check("PCMatApply_GenEO", std::min(ldx, ldy), m, X, Y)) return rc;
+  try {
+    const int w = blk_w;
+    for (int j0 = 0; j0 < m; j0 += w) {
+      const int ms = std::min(w, m - j0);
+      slab_in(X + (size_t)j0 * ldx, ldx, ms, blk_in);
+      apply_block(blk_in, blk_out);
+      slab_out(blk_out, ms, Y + (size_t)j0 * ldy, ldy);
+      blk_slabs += 1;
+      blk_columns += ms;
+      blk_padded += w - ms;
+    }
+  } catch (std::exception& e) {
+    return fail(e.what());
+  }
+  return 0;
+}
+
+int PC::matmult_mat(const double* X, int ldx, double* Y, int ldy, int m) {
+  if (int rc = block_check("MatMatMult_GenEO", std::min(ldx, ldy), m, X, Y)) return rc;
+  try {
+    const int w = blk_w;
+    for (int j0 = 0; j0 < m; j0 += w) {
+      const int ms = std::min(w, m - j0);
+      slab_in(X + (size_t)j0 * ldx, ldx, ms, blk_in);
+      matmult_block(blk_in, blk_out, w, blk_r0, blk_xe);
+      slab_out(blk_out, ms, Y + (size_t)j0 * ldy, ldy);
+    }
   } catch (std::exception& e) {
     return fail(e.what());
   }
@@ -3807,6 +4306,139 @@ int PC::solve_cg(const double* b, double* x, KspResult* res) {
   }
   res->reason = -3;
   return done(0);
+}
+
+// h_out[j] = sum over ALL ranks of X[:, j] . Y[:, j] on owned slabs: one kernel pair, one all-reduce of w, one download
+void PC::slab_coldot(const double* X, const double* Y, double* h_out) {
+  const int w = blk_w;
+  if (g_block_fused.load()) bk::block_coldot(X, Y, n_owned(), w, blk_dots, blk_dotwork);
+  else block_coldot_composed_once(X, Y, n_owned(), w, blk_dots);
+  allreduce(blk_dots, w);
+  bk::d2h(h_out, blk_dots, sizeof(double) * w);
+}
+// xpby: A[:, j] = B[:, j] + c[j] A[:, j];  else: A[:, j] += c[j] B[:, j]  (c: w host values, uploaded here)
+void PC::slab_cols(bool xpby, double* A, const double* B, const double* h_c) {
+  const int w = blk_w, n = n_owned();
+  double* c = blk_coef + (xpby ? 0 : w);
+  bk::h2d(c, h_c, sizeof(double) * w);
+  const bool fused = g_block_fused.load() != 0;
+  if (xpby) fused ? bk::block_xpby_cols(A, B, c, n, w) : block_xpby_cols_composed_once(A, B, c, n, w);
+  else fused ? bk::block_axpy_cols(A, B, c, n, w) : block_axpy_cols_composed_once(A, B, c, n, w);
+  bk::sync();      // the next upload may reuse the coefficient slot
+}
+
+// solve_cg on every column of a block, in lock step, zero initial guess.  Per iteration one column-dot kernel and one
+// all-reduce of w for each of beta, p.Ap and |z|^2; the scalars go to the host, every column runs its own ConvTest, and the
+// coefficients go back.  A column that met its test (or hit beta == 0 or p.Ap <= 0) is frozen: its coefficients are exactly
+// 0 from then on, so its x and r stop changing (its p becomes z, which repeats, and is never used again), and its
+// its / rnorm / reason are those of that moment.
+int PC::solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason) {
+  const int n = n_owned(), w = blk_w, nw = slab_entries(n, w);
+  DeviceVectors bufs;
+  auto dv = [&](void) { return bufs.get(nw); };
+  double *x = dv(), *r = dv(), *z = dv(), *p = dv(), *q = dv();
+  std::vector<double> beta(w), betaold(w), dpi(w), zz(w), ca(w), cb(w);
+  auto applied = [&](int ms) {
+    blk_slabs += 1;
+    blk_columns += ms;
+    blk_padded += w - ms;
+  };
+  for (int j0 = 0; j0 < m; j0 += w) {
+    const int ms = std::min(w, m - j0);
+    std::vector<ConvTest> conv(ms, ConvTest{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol});
+    std::vector<char> frozen(w, 1);          // the padding columns never take part
+    int* it = its + j0;
+    double* rn = rnorm + j0;
+    int* rs = reason + j0;
+    slab_in(B + (size_t)j0 * ldb, ldb, ms, r);      // x = 0: r = b
+    bk::zero(x, sizeof(double) * (size_t)nw);
+    apply_block(r, z);
+    applied(ms);
+    slab_coldot(z, z, zz.data());
+    int active = 0;
+    for (int j = 0; j < ms; ++j) {
+      const double dp = std::sqrt(zz[j]);
+      it[j] = 0;
+      rn[j] = dp;
+      rs[j] = conv[j](0, dp, -1.0);
+      frozen[j] = rs[j] != 0;
+      active += !frozen[j];
+      betaold[j] = 0.0;
+    }
+    for (int i = 0; i < opt.ksp_max_it && active > 0; ++i) {
+      slab_coldot(z, r, beta.data());
+      for (int j = 0; j < w; ++j) {
+        cb[j] = 0.0;
+        if (frozen[j]) continue;
+        it[j] = i + 1;
+        if (beta[j] == 0.0) {
+          rs[j] = 3;
+          frozen[j] = 1;
+          --active;
+        } else if (i > 0) {
+          cb[j] = beta[j] / betaold[j];
+        }
+      }
+      if (active == 0) break;
+      if (i == 0) bk::copy(p, z, nw);
+      else slab_cols(true, p, z, cb.data());        // p = z + b p
+      matmult_block(p, q, w, blk_r0, blk_xe);
+      slab_coldot(p, q, dpi.data());
+      for (int j = 0; j < w; ++j) {
+        ca[j] = 0.0;
+        if (frozen[j]) continue;
+        betaold[j] = beta[j];
+        if (!(dpi[j] > 0.0)) {                       // KSP_DIVERGED_INDEFINITE_MAT
+          rs[j] = -8;
+          frozen[j] = 1;
+          --active;
+        } else {
+          ca[j] = beta[j] / dpi[j];
+        }
+      }
+      if (active == 0) break;
+      slab_cols(false, x, p, ca.data());
+      for (int j = 0; j < w; ++j) ca[j] = -ca[j];
+      slab_cols(false, r, q, ca.data());
+      apply_block(r, z);
+      applied(ms);
+      slab_coldot(z, z, zz.data());
+      for (int j = 0; j < ms; ++j) {
+        if (frozen[j]) continue;
+        const double dp = std::sqrt(zz[j]);
+        rn[j] = dp;
+        rs[j] = conv[j](i + 1, dp, -1.0);
+        if (rs[j]) {
+          frozen[j] = 1;
+          --active;
+        }
+      }
+    }
+    for (int j = 0; j < ms; ++j)
+      if (!frozen[j]) rs[j] = -3;
+    slab_out(x, ms, X + (size_t)j0 * ldx, ldx);
+  }
+  return 0;
+}
+
+int PC::solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason) {
+  if (int rc = block_check("KSPMatSolve_GenEO", std::min(ldb, ldx), m, B, X)) return rc;
+  if (!its || !rnorm || !reason) return fail("KSPMatSolve_GenEO: its, rnorm and reason need m entries each");
+  if (opt.ksp_type != "cg")
+    return fail("KSPMatSolve_GenEO: -ksp_type " + opt.ksp_type + " has no block form (the block Krylov method is -ksp_type cg)");
+  if (opt.ksp_guess_nonzero)
+    return fail("KSPMatSolve_GenEO: -ksp_initial_guess_nonzero is not supported (the block solve starts from zero: "
+                "-ksp_initial_guess_nonzero 0)");
+  auto t0 = clk::now();
+  int rc = 0;
+  try {
+    rc = solve_cg_block(B, ldb, X, ldx, m, its, rnorm, reason);
+  } catch (std::exception& e) {
+    return fail(e.what());
+  }
+  bk::sync();
+  info.solveTime = secs(t0, clk::now());
+  return rc;
 }
 
 // KSPSolve_GMRES (PETSc gmres.c): left preconditioning, classical Gram-Schmidt, Givens residual

@@ -97,6 +97,11 @@ struct Options {
   enum CoarseDevice { COARSE_AUTO = 0, COARSE_NEVER = 1, COARSE_ALWAYS = 2 };
   int coarse_device = COARSE_AUTO;
   int coarse_block = 128;   // within 7 % of the best sweeps and 1.5 x of the best factor time at 1256 .. 5120
+  // -geneo_block_width 0|16|32: slab width of the block entry points (PCMatApply_GenEO, MatMatMult_GenEO,
+  // KSPMatSolve_GenEO).  0: none -- the set-up allocates and builds nothing for them.  16 | 32: needs -dls1_ksp_type
+  // chebyshev (a fixed linear operator: the block local solve is its chain of launches with SpMM in place of SpMV).  Read
+  // by the set-up: a change afterwards has no effect before the next set-up.
+  int block_width = 0;
   bool dls1_amg_single = true;   // -dls1_amg_precision single|double: storage of the level matrices the V-cycle of the local solves reads
   // Krylov driver (counterpart of the PETSc KSP the reference calls at driver:1240)
   std::string ksp_type = "gmres";
@@ -124,6 +129,29 @@ bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, con
                        const double* dscale, double* out, const ChebWork& w);
 bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
                             const double* dscale, double* out);
+
+// validation switch "block_fused": 1 (default) the kernels of block_dev.h, 0 the same operations composed of backend.h
+// primitives (the definitions the host twin links)
+void set_block_fused(int on);
+int block_fused();
+struct BlockWork {   // scratch of the composed block step: one slab, the coefficients spread over the columns, their gather indices
+  double *t = nullptr, *ab = nullptr;
+  int* idx = nullptr;
+  int n = 0, ns = 0, w = 0;
+  void alloc(int n, int ns, int w);
+  void release();
+};
+// core.cpp: the operations of block_dev.h from backend.h primitives; the _once forms allocate their scratch, run, wait, free
+bool cheb_dir_block_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                             const double* dscale, double* Out, int w, const BlockWork& wk);
+bool cheb_dir_block_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                                  const double* dscale, double* Out, int w);
+bool block_import_composed(const double* Xcm, int ld, int n, int m, double* Yrm, int w);
+bool block_export_composed(const double* Xrm, int w, int n, int m, double* Ycm, int ld);
+bool block_coldot_composed_once(const double* X, const double* Y, int n, int w, double* out);
+bool block_axpy_cols_composed_once(double* Y, const double* X, const double* c, int n, int w);
+bool block_xpby_cols_composed_once(double* P, const double* Z, const double* c, int n, int w);
+bool chol_solve_block_composed_once(const double* L, const double* LT, int n, double* Y, int w);
 
 struct Info {                 // public counters / timers of geneoContext (hdr/geneo.hpp:96-123)
   int estimDimELoc = 0, realDimELoc = 0, nicolaidesLoc = 0, dimE = 0;
@@ -195,6 +223,15 @@ class PC {
   std::vector<int> cheb_its;
   int matmult(const double* x_dev, double* y_dev);      // MatMult(MATIS)
   int solve(const double* b_dev, double* x_dev, KspResult* res);  // KSPSolve counterpart
+  // ---- blocks of right-hand sides (-geneo_block_width 16 | 32): column-major n_owned x m blocks with a leading dimension,
+  // processed in slabs of the width (the last one zero-padded).  Each returns an error for a set-up without a width.
+  int apply_mat(const double* X, int ldx, double* Y, int ldy, int m);        // PCMatApply: Y = M^-1 X
+  int matmult_mat(const double* X, int ldx, double* Y, int ldy, int m);      // MatMatMult: Y = A X
+  // KSPMatSolve: PCG on every column in lock step, zero initial guess (X is zeroed here); its / rnorm / reason: m entries
+  int solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
+  // since the set-up: slabs applied by apply_mat (KSPMatSolve's included), their columns, the zero columns that padded
+  // them, and the local solves of slabs replayed from the HIP graph (the others went out as direct launches)
+  void block_info(int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) const;
   int n_owned() const { return (int)owned.size(); }
   int cheb_steps_per_solve() const { return cheb_K; }
   void cheb_counters(long long* solves, long long* graph_launches, long long* fused_residuals) const {
@@ -280,6 +317,36 @@ class PC {
   void cheb_release();
   int cheb_steps(double* wL, const double* dscale);   // returns the number of residual updates bk::cheb_residual took
   void local_solve_cheb(double* wL);
+  // Block entry points: slab width of this set-up (0: none), the work space (local slabs r -- two, ping-pong --, z, d, x;
+  // owned slabs in / out / t1..t3; the ext staging slab; coarse right-hand sides, per-subdomain Gram rows and
+  // coefficients), the row-major Z, the index maps between Gram rows, coarse rows and coefficient rows, the HIP graph of
+  // one slab's local solve, and the counters of PCGenEOGetBlockInfo
+  int blk_w = 0, blk_kp = 0;
+  double *blk_r0 = nullptr, *blk_r1 = nullptr, *blk_z = nullptr, *blk_d = nullptr, *blk_x = nullptr;
+  double *blk_in = nullptr, *blk_out = nullptr, *blk_t1 = nullptr, *blk_t2 = nullptr, *blk_t3 = nullptr, *blk_xe = nullptr;
+  double *blk_yE = nullptr, *blk_G = nullptr, *blk_C = nullptr, *blk_ZR = nullptr, *blk_col = nullptr;
+  double *blk_dots = nullptr, *blk_dotwork = nullptr, *blk_coef = nullptr;
+  int *blk_g2e = nullptr, *blk_e2c = nullptr;
+  void* blk_graph = nullptr;
+  int blk_graph_fused = -1;
+  bool blk_graph_failed = false;
+  long long blk_slabs = 0, blk_columns = 0, blk_padded = 0, blk_graph_launches = 0, blk_solves = 0;
+  BlockWork blk_work;
+  int setup_block();
+  void block_release();
+  int block_check(const char* who, int ld, int m, const void* a, const void* b);
+  void block_steps(const double* dscale);
+  void local_solve_block();                                        // on blk_r0
+  void coarse_einv_block(double* YE);
+  void coarse_solve_block(const double* XL);                       // blk_C = per-subdomain rows of E^-1 Z^T X (from XL)
+  void apply_q_block(const double* X, double* Y);
+  void apply_block(const double* X, double* Y);                    // owned slabs, mirrors apply() branch for branch
+  void slab_in(const double* Xcm, int ld, int m, double* slab);
+  void slab_out(const double* slab, int m, double* Ycm, int ld);
+  void slab_coldot(const double* X, const double* Y, double* h_out);
+  void slab_cols(bool xpby, double* A, const double* B, const double* h_c);
+  int solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
+  void coarse_einv(double* yE);                                    // yE <- E^-1 yE (the factor's own path)
   HostCsr host_neu_cache, host_dir_cache;   // block-diagonal host copies of A_Neu / the level-1 matrix, reused by the next set-up
   AmgDevice* amg1 = nullptr;   // hierarchy of the level-1 (Dirichlet / Robin) block-diagonal matrix (local solves)
   AmgDevice* amgN = nullptr;   // hierarchy of the Neumann block-diagonal matrix (LOBPCG preconditioner)

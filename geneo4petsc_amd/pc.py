@@ -246,6 +246,46 @@ class GenEOPC:
         x = xd if isinstance(b, DeviceVector) else xd.to_host()
         return x, its.value, rnorm.value, KSP_REASONS.get(reason.value, str(reason.value))
 
+    # -- blocks of right-hand sides (-geneo_block_width 16 | 32) ----------------------------------
+    def _block(self, fn, X):
+        """X: (n_owned, m) array.  Staged column-major with ld = n_owned; returns the (n_owned, m) result."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise GenEOError("a block of right-hand sides is a 2-d array (n_owned, m)")
+        n, m = X.shape
+        xd = DeviceVector.from_host(self.lib, np.asfortranarray(X).ravel(order="F"))
+        yd = DeviceVector(self.lib, n * max(1, m))
+        out = fn(xd, yd, n, m)
+        Y = yd.to_host()[:n * m].reshape((n, m), order="F")
+        return Y if out is None else (Y,) + out
+
+    def mat_apply(self, X):
+        """PCMatApply_GenEO: M^-1 on every column of X, in slabs of the block width."""
+        return self._block(lambda xd, yd, n, m: self._chk(self.lib.PCMatApply_GenEO(self.h, xd.ptr, n, yd.ptr, n, m)), X)
+
+    def mat_mult(self, X):
+        """MatMatMult_GenEO: the MATIS operator on every column of X."""
+        return self._block(lambda xd, yd, n, m: self._chk(self.lib.MatMatMult_GenEO(self.h, xd.ptr, n, yd.ptr, n, m)), X)
+
+    def mat_solve(self, B):
+        """KSPMatSolve_GenEO: block PCG from a zero initial guess.  Returns (X, its, rnorm, reasons) with one entry per
+        column; reasons are the KSPConvergedReason names."""
+        def run(bd, xd, n, m):
+            its, rs, rn = np.zeros(max(1, m), dtype=np.int32), np.zeros(max(1, m), dtype=np.int32), np.zeros(max(1, m))
+            self._chk(self.lib.KSPMatSolve_GenEO(self.h, bd.ptr, n, xd.ptr, n, m, its.ctypes.data_as(L.c_int_p),
+                                                 rn.ctypes.data_as(L.c_dbl_p), rs.ctypes.data_as(L.c_int_p)))
+            return its[:m], rn[:m], [KSP_REASONS.get(int(r), str(int(r))) for r in rs[:m]]
+        return self._block(run, B)
+
+    def block_info(self):
+        """PCGenEOGetBlockInfo since the set-up: width, slabs and columns through the block apply, zero columns that padded
+        them, local solves of slabs replayed from the HIP graph."""
+        w = C.c_int(0)
+        v = [C.c_longlong(0) for _ in range(4)]
+        if self.lib.PCGenEOGetBlockInfo(self.h, C.byref(w), *[C.byref(x) for x in v]) < 0:
+            raise GenEOError("PCGenEOGetBlockInfo: bad handle")
+        return dict(width=w.value, slabs=v[0].value, columns=v[1].value, padded=v[2].value, graph_launches=v[3].value)
+
     def residual_history(self):
         n = self.lib.PCGenEOGetResidualHistory(self.h, None, 0)
         out = np.zeros(max(1, n))

@@ -185,6 +185,33 @@ PetscErrorCode PCGenEOSetRHS(GENEO_PC pc, const double* b_dev);
 PetscErrorCode KSPSolve_GenEO(GENEO_PC pc, const double* b_dev, double* x_dev, int* its, double* rnorm, int* reason);
 int PCGenEOGetResidualHistory(GENEO_PC pc, double* hist, int cap);
 
+/* ---- blocks of right-hand sides (-geneo_block_width 16 | 32; needs -dls1_ksp_type chebyshev) --------------------------
+ * The counterparts of pc->ops->matapply, MatMatMult on the MATIS operator and KSPMatSolve.  Blocks are column-major with a
+ * leading dimension, as PETSc's MatDense holds them: n_owned rows, m >= 1 columns, ld >= n_owned, device memory.  Columns
+ * are processed in slabs of the width; the last slab is padded with zero columns, which stay exactly zero through every
+ * linear step and are never written back.  Bytes of the output beyond column m and between row n_owned and ld are not
+ * touched.
+ * The local solve of a slab is the fixed chain of launches of the Chebyshev local solver with SpMM in place of SpMV,
+ * replayed from a HIP graph of its own.  Its V-cycle reads the FP64 level matrices: under -dls1_amg_precision single the
+ * single-vector path reads their float companions and the two are slightly different (fixed, linear, symmetric)
+ * operators; under -dls1_amg_precision double they differ by summation order alone.
+ * KSPMatSolve_GenEO: preconditioned CG on every column in lock step with a zero initial guess (X is zeroed by the library);
+ * every column runs its own convergence test and is frozen once it has met it.  its / rnorm / reason: m entries each, host.
+ * -ksp_type gmres and -ksp_initial_guess_nonzero (the default of this library: pass -ksp_initial_guess_nonzero 0) are
+ * refused.  PCGenEOGetResidualHistory is not extended to blocks.
+ * Each returns an error, not a crash, for a set-up without -geneo_block_width, a PC that is not set up, ld < n_owned and
+ * m < 1.  The width is read by the set-up: changing the option afterwards has no effect before the next set-up. */
+PetscErrorCode PCMatApply_GenEO(GENEO_PC pc, const double* X_dev, int ldx, double* Y_dev, int ldy, int m);
+PetscErrorCode MatMatMult_GenEO(GENEO_PC pc, const double* X_dev, int ldx, double* Y_dev, int ldy, int m);
+PetscErrorCode KSPMatSolve_GenEO(GENEO_PC pc, const double* B_dev, int ldb, double* X_dev, int ldx, int m, int* its,
+                                 double* rnorm, int* reason);
+/* Since the set-up: the width, the slabs that went through the block apply (KSPMatSolve_GenEO's included), their columns,
+ * the zero columns that padded them, and the local solves of slabs replayed from the HIP graph (the others went out as
+ * direct launches: the first one, one in eight while the in-situ kernel timer runs, and all of them where capture is
+ * unavailable).  Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
+int PCGenEOGetBlockInfo(GENEO_PC pc, int* width, long long* slabs, long long* columns, long long* padded,
+                        long long* graph_launches);
+
 /* ---- public counters / timers of geneoContext (hdr/geneo.hpp:96-123) ----------------------- */
 typedef struct {
   int estimDimELoc, realDimELoc, nicolaidesLoc, dimE;
@@ -309,7 +336,8 @@ PetscErrorCode GeneoSetMFMA(int enable);         /* 0: run the plain-FMA twins o
  * the hash table as well), "gram_flat" (0: k_gram_mfma instead of k_gram_flat); both forms of each give bit-identical
  * results (tests/test_gpu_kernels.py).  "cheb_fused" (0: the step of the Chebyshev local solver composed of the plain
  * vector primitives and its residual update as the plain product and a vector update, instead of their fused kernels;
- * same bits).  Returns 1 for an unknown name. */
+ * same bits).  "block_fused" (0: the operations of the block entry points composed of the plain primitives instead of
+ * the kernels of csrc/block_dev.h; same bits in PCMatApply_GenEO).  Returns 1 for an unknown name. */
 PetscErrorCode GeneoSetKernelVariant(const char* name, int value);
 
 /* ---- stand-alone kernels (parity tests and the roofline leg of bench.py) --------------------- */
@@ -393,6 +421,9 @@ PetscErrorCode GeneoTestLobpcgUpdate(int nsub, const int* suboff, const double* 
  * Returns the primitive's own result (void: 0, bool: 0 / 1, recip_positive: its count), -1 on an error
  * (PCGenEOGetError(NULL)), -2 for an unknown name. */
 int GeneoTestPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
+/* The same for the primitives of the block entry points (csrc/block_dev.h); argument table in tests/block_rhs_util.py.
+ * Returns the primitive's bool as 0 / 1, -1 on an error, -2 for an unknown name. */
+int GeneoTestBlockPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
 
 /* ---- the coarse operator E on the device at any dimE (-geneo_coarse_device auto|never|always, -geneo_coarse_block nb) ----
  * Where this PC factored E and how it applies E^-1, after the set-up.  factor_on_device: 1 when the blocked device
