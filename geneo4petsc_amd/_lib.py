@@ -178,6 +178,13 @@ SYMBOLS = {
     "GeneoTestCgSteps": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 + [c_dbl_p]),
     "GeneoTestCsrOp": (C.c_longlong, [C.c_int, C.POINTER(GeneoCsr), C.POINTER(GeneoCsr), c_int_p, c_dbl_p, C.POINTER(C.c_void_p),
                        c_int_p, c_int_p, c_dbl_p, C.c_longlong]),
+    "GeneoTestAmgCreate": (C.c_int, [C.POINTER(GeneoCsr), C.c_int, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
+    "GeneoTestAmgDestroy": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "GeneoTestAmgInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_int_p]),
+    "GeneoTestAmgLevel": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), c_dbl_p, c_int_p, c_dbl_p]),
+    "GeneoTestAmgMatrix": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_dbl_p, C.c_longlong]),
+    "GeneoTestAmgCoarseInverse": (C.c_longlong, [C.c_void_p, C.POINTER(C.c_longlong), c_dbl_p, C.c_longlong]),
+    "GeneoTestAmgVcycle": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p, C.c_int, C.c_int]),
 }
 
 

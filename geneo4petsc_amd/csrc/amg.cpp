@@ -941,7 +941,14 @@ void AmgDevice::smooth(Lvl& L, const double* B, int ldb, double* X, int ldx, int
   }
 }
 
-void AmgDevice::cycle(int l, const double* B, int ldb, double* X, int ldx, int m) {
+// Contiguous single vectors read the single-precision companions -- only when the hierarchy was asked to use them
+// (-dls1_amg_precision single): a borrowed level-0 matrix may carry a companion for its owner's own purposes (the 16-bit
+// column offsets of the FP64 SpMV), which must not turn a "double" V-cycle into a float one.  The caller's vectors
+// decide for every level: the coarse levels of a cycle on a strided vector (whose fine level runs the FP64 block
+// kernels) are contiguous, and would otherwise read float entries under an FP64 fine level.
+bool AmgDevice::lp_cycle(int ldb, int ldx, int m) const { return m == 1 && ldb <= 1 && ldx <= 1 && prm.single; }
+
+void AmgDevice::cycle(int l, const double* B, int ldb, double* X, int ldx, int m, bool vec) {
   Lvl& L = lv[l];
   if (l == (int)lv.size() - 1) {
     bk::dense_sym_apply(cch, d_inv, d_invbase, B, ldb, X, ldx, m);
@@ -952,17 +959,14 @@ void AmgDevice::cycle(int l, const double* B, int ldb, double* X, int ldx, int m
     // damped-Jacobi V-cycle in 4 launches per level: the vector passes ride on the SpMV / SpMM epilogues
     const double w = jacobi_weight(L);
     const bk::Csr& Apre = L.Acs.n ? L.Acs : L.A;
-    // contiguous single vectors: the single-precision companions apply -- only when the hierarchy was asked to use them
-    // (-dls1_amg_precision single): a borrowed level-0 matrix may carry a companion for its owner's own purposes (the
-    // 16-bit column offsets of the FP64 SpMV), which must not turn a "double" V-cycle into a float one
-    const bool vec = (m == 1 && ldb <= 1 && ldx <= 1) && prm.single;
+    // vec: the single-precision companions apply (lp_cycle: decided once for the whole cycle, not level by level)
     // with the post-smoothing matrix x1 = w D^-1 b is never read back (EPI_POST rebuilds it from b): it is not stored
     double* X1 = L.M.n ? nullptr : X;
     if (vec && bk::csr_has_lp(Apre)) bk::spmv_fused_lp(Apre, bk::EPI_PRE, nullptr, L.r, B, X1, L.dinv, w);
     else bk::spmm_fused(Apre, bk::EPI_PRE, nullptr, 0, L.r, m, m, B, ldb, X1, ldx, L.dinv, w);   // x1 = w D^-1 b ; r1 = b - A x1
     if (vec && bk::csr_has_lp(L.R)) bk::spmv_lp(L.R, L.r, C0.b);
     else applyA(L.R, L.r, m, C0.b, m, m);                                                   // restrict
-    cycle(l + 1, C0.b, m, C0.x, m, m);
+    cycle(l + 1, C0.b, m, C0.x, m, m, vec);
     if (L.M.n) {      // x = w D^-1 (b + r1) + (P - w D^-1 A P) e
       if (vec && bk::csr_has_lp(L.M)) bk::spmv_fused_lp(L.M, bk::EPI_POST, C0.x, X, L.r, const_cast<double*>(B), L.dinv, w);
       else bk::spmm_fused(L.M, bk::EPI_POST, C0.x, m, X, ldx, m, L.r, m, const_cast<double*>(B), ldb, L.dinv, w);
@@ -979,7 +983,7 @@ void AmgDevice::cycle(int l, const double* B, int ldb, double* X, int ldx, int m
   bk::block_axpby(L.r, m, 1.0, B, ldb, -1.0, L.n, m);
   Lvl& C = lv[l + 1];
   applyA(L.R, L.r, m, C.b, m, m);                                          // restrict
-  cycle(l + 1, C.b, m, C.x, m, m);
+  cycle(l + 1, C.b, m, C.x, m, m, vec);
   applyA(L.P, C.x, m, L.d, m, m);                                          // prolong + correct
   bk::block_axpby(X, ldx, 1.0, L.d, m, 1.0, L.n, m);
   smooth(L, B, ldb, X, ldx, m, false);                                     // post-smoothing
@@ -988,12 +992,12 @@ void AmgDevice::cycle(int l, const double* B, int ldb, double* X, int ldx, int m
 void AmgDevice::vcycle_from(int l, const double* B, int ldb, double* X, int ldx, int m) {
   if (m > maxm) throw std::runtime_error("AMG: block wider than the hierarchy was allocated for");
   if (l < 0 || l >= (int)lv.size()) throw std::runtime_error("AMG: no such level");
-  cycle(l, B, ldb, X, ldx, m);
+  cycle(l, B, ldb, X, ldx, m, lp_cycle(ldb, ldx, m));
 }
 
 void AmgDevice::vcycle(const double* B, int ldb, double* X, int ldx, int m) {
   if (m > maxm) throw std::runtime_error("AMG: block wider than the hierarchy was allocated for");
-  cycle(0, B, ldb, X, ldx, m);
+  cycle(0, B, ldb, X, ldx, m, lp_cycle(ldb, ldx, m));
 }
 
 }  // namespace geneo

@@ -83,6 +83,14 @@ class AmgDevice {
   const double* level_dinv(int l) const { return lv[l].dinv; }
   int level_rows(int l) const { return lv[l].n; }
   const std::vector<int>& level_suboff(int l) const { return lv[l].suboff; }
+  // The rest of a level, read only, for the test hooks (GeneoTestAmg*, capi.cpp): the derived matrices (n == 0: the level
+  // has none), the Gershgorin bound, the form of the cycle, and the coarsest dense inverses with their bases (device).
+  const bk::Csr& level_Acs(int l) const { return lv[l].Acs; }
+  const bk::Csr& level_M(int l) const { return lv[l].M; }
+  double level_rho(int l) const { return lv[l].rho; }
+  bool level_fused(int l) const { return lv[l].fused; }
+  const double* coarsest_inv() const { return d_inv; }
+  const int64_t* coarsest_inv_base() const { return d_invbase; }
 
  private:
   struct Lvl {
@@ -114,7 +122,8 @@ class AmgDevice {
   double jacobi_weight(const Lvl& L) const;
   void applyA(const bk::Csr& a, const double* X, int ldx, double* Y, int ldy, int m);
   void smooth(Lvl& L, const double* B, int ldb, double* X, int ldx, int m, bool zero_guess);
-  void cycle(int l, const double* B, int ldb, double* X, int ldx, int m);
+  bool lp_cycle(int ldb, int ldx, int m) const;
+  void cycle(int l, const double* B, int ldb, double* X, int ldx, int m, bool vec);
 };
 
 }  // namespace geneo

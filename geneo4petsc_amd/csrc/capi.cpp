@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "../../include/geneo_c.h"
+#include "amg.h"
 #include "block_dev.h"
 #include "cheb_dev.h"
 #include "coarse_dev.h"
@@ -34,6 +35,17 @@ struct _p_GeneoPC {
 struct _p_GeneoSpmv {
   bk::Csr a;
 };
+
+struct _p_GeneoTestAmg {
+  geneo::AmgDevice dev;
+  bk::Csr fine;               // the level-0 matrix: uploaded by the hook, borrowed by the hierarchy (fine_dev)
+};
+static void test_amg_free(_p_GeneoTestAmg* h) {
+  if (!h) return;
+  h->dev.free_all();          // before the matrix its level 0 borrows
+  bk::csr_free(h->fine);
+  delete h;
+}
 
 static std::string g_global_err;
 
@@ -1286,6 +1298,168 @@ long long GeneoTestCsrOp(int op, const GeneoCsr* A, const GeneoCsr* B, const int
     g_global_err = e.what();
     return -2;
   }
+}
+
+// ---- a stand-alone multigrid hierarchy (test hook): created from a host matrix, read back level by level, and its cycle
+// applied to host blocks.  No arithmetic here: upload, AmgDevice, download.
+int GeneoTestAmgCreate(const GeneoCsr* A, int nsub, const int* suboff, const int* iparam, const double* dparam,
+                       GeneoTestAmg* out) {
+  if (!out) return 1;
+  *out = nullptr;
+  _p_GeneoTestAmg* h = nullptr;
+  try {
+    if (!A || !suboff || !iparam || !dparam || nsub < 1 || A->n < 1) throw std::runtime_error("GeneoTestAmgCreate: bad arguments");
+    if (suboff[0] != 0 || suboff[nsub] != A->n) throw std::runtime_error("GeneoTestAmgCreate: suboff must run from 0 to the matrix size");
+    for (int s = 0; s < nsub; ++s)
+      if (suboff[s + 1] < suboff[s]) throw std::runtime_error("GeneoTestAmgCreate: suboff must ascend");
+    geneo::HostCsr ha;
+    ha.n = A->n;
+    ha.rowptr.assign(A->rowptr, A->rowptr + A->n + 1);
+    ha.col.assign(A->col, A->col + A->rowptr[A->n]);
+    ha.val.assign(A->val, A->val + A->rowptr[A->n]);
+    geneo::AmgParams prm;
+    prm.coarse_size = iparam[0];
+    prm.smooth_degree = iparam[1];
+    prm.max_levels = iparam[2];
+    prm.single = iparam[3] != 0;
+    const int max_m = iparam[4];
+    prm.smooth_ratio = dparam[0];
+    prm.strength = dparam[1];
+    const std::vector<int> so(suboff, suboff + nsub + 1);
+    h = new _p_GeneoTestAmg();
+    h->fine = bk::csr_upload(A->n, A->rowptr, A->col, A->val);
+    if (iparam[6] && !bk::csr_make_lp(h->fine)) throw std::runtime_error("GeneoTestAmgCreate: no single-precision companion for the fine matrix");
+    bool built = true;
+    if (iparam[5] == 0) {
+      built = h->dev.build_on_device(ha, so, prm, max_m, &h->fine);
+    } else {
+      std::vector<geneo::AmgLevelHost> levels;
+      std::vector<double> cinv;
+      std::vector<int64_t> cbase;
+      geneo::amg_setup_host(ha, so, prm, levels, cinv, cbase);
+      h->dev.upload(levels, cinv, cbase, prm, max_m, &h->fine);
+    }
+    bk::sync();
+    if (!built) {
+      test_amg_free(h);
+      return 2;
+    }
+    *out = h;
+    return 0;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    try { test_amg_free(h); } catch (...) {}
+    return 1;
+  }
+}
+
+int GeneoTestAmgDestroy(GeneoTestAmg* h) {
+  if (!h || !*h) return 0;
+  GUARD_BEGIN
+  test_amg_free(*h);
+  *h = nullptr;
+  GUARD_END((PC) nullptr)
+  return 0;
+}
+
+int GeneoTestAmgInfo(GeneoTestAmg h, int* nlevels, double* operator_complexity, int* lp_matrices) {
+  if (!h) return 1;
+  if (nlevels) *nlevels = h->dev.nlevels();
+  if (operator_complexity) *operator_complexity = h->dev.operator_complexity();
+  if (lp_matrices) *lp_matrices = h->dev.lp_matrices();
+  return 0;
+}
+
+static const bk::Csr* test_amg_matrix(_p_GeneoTestAmg* h, int level, int which) {
+  if (level < 0 || level >= h->dev.nlevels()) throw std::runtime_error("GeneoTestAmg: no such level");
+  switch (which) {
+    case 0: return &h->dev.level_A(level);
+    case 1: return &h->dev.level_P(level);
+    case 2: return &h->dev.level_R(level);
+    case 3: return &h->dev.level_M(level);
+    case 4: return &h->dev.level_Acs(level);
+  }
+  throw std::runtime_error("GeneoTestAmg: no such matrix");
+}
+
+int GeneoTestAmgLevel(GeneoTestAmg h, int level, long long* iout, double* rho, int* suboff, double* dinv) {
+  if (!h) return 1;
+  GUARD_BEGIN
+  const bk::Csr& a = *test_amg_matrix(h, level, 0);
+  const std::vector<int>& so = h->dev.level_suboff(level);
+  const int n = h->dev.level_rows(level);
+  if (iout) {
+    iout[0] = n;
+    iout[1] = (long long)so.size() - 1;
+    iout[2] = h->dev.level_fused(level) ? 1 : 0;
+    iout[3] = a.vec_lpr;
+    iout[4] = a.nlong;
+    iout[5] = 0;
+    for (int w = 0; w < 5; ++w) {
+      const bk::Csr& m = *test_amg_matrix(h, level, w);
+      iout[6 + w] = m.n ? (long long)m.nnz : -1;          // -1: the level has no such matrix
+      if (m.n && bk::csr_has_lp(m)) iout[5] |= 1LL << w;
+    }
+  }
+  if (rho) *rho = h->dev.level_rho(level);
+  if (suboff) std::copy(so.begin(), so.end(), suboff);
+  if (dinv) bk::d2h(dinv, h->dev.level_dinv(level), sizeof(double) * (size_t)n);
+  GUARD_END((PC) nullptr)
+  return 0;
+}
+
+long long GeneoTestAmgMatrix(GeneoTestAmg h, int level, int which, int* rows, int* rowptr, int* col, double* val, long long cap) {
+  if (!h) return -2;
+  try {
+    const bk::Csr& m = *test_amg_matrix(h, level, which);
+    if (!m.n) return -1;
+    if (rows) *rows = m.n;
+    if (cap >= (long long)m.nnz && rowptr && col && val) bk::csr_download(m, rowptr, col, val);
+    return (long long)m.nnz;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -2;
+  }
+}
+
+long long GeneoTestAmgCoarseInverse(GeneoTestAmg h, long long* base, double* inv, long long cap) {
+  if (!h || !base) return -2;
+  try {
+    static_assert(sizeof(long long) == sizeof(int64_t), "bases are downloaded as they lie");
+    const int nsub = (int)h->dev.level_suboff(h->dev.nlevels() - 1).size() - 1;
+    bk::d2h(base, h->dev.coarsest_inv_base(), sizeof(int64_t) * ((size_t)nsub + 1));
+    if (cap >= base[nsub] && inv) bk::d2h(inv, h->dev.coarsest_inv(), sizeof(double) * (size_t)base[nsub]);
+    return base[nsub];
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -2;
+  }
+}
+
+int GeneoTestAmgVcycle(GeneoTestAmg h, int level, double* B, int ldb, double* X, int ldx, int m) {
+  if (!h) return 1;
+  GUARD_BEGIN
+  if (!B || !X || m < 1 || ldb < m || ldx < m) throw std::runtime_error("GeneoTestAmgVcycle: bad arguments");
+  if (level < 0 || level >= h->dev.nlevels()) throw std::runtime_error("GeneoTestAmg: no such level");
+  const size_t n = (size_t)h->dev.level_rows(level);
+  double *b = nullptr, *x = nullptr;
+  try {
+    b = (double*)bk::alloc(sizeof(double) * n * ldb);
+    x = (double*)bk::alloc(sizeof(double) * n * ldx);
+    bk::h2d(b, B, sizeof(double) * n * ldb);
+    bk::h2d(x, X, sizeof(double) * n * ldx);
+    h->dev.vcycle_from(level, b, ldb, x, ldx, m);
+    bk::d2h(X, x, sizeof(double) * n * ldx);
+    bk::d2h(B, b, sizeof(double) * n * ldb);
+  } catch (...) {
+    bk::dfree(b);
+    bk::dfree(x);
+    throw;
+  }
+  bk::dfree(b);
+  bk::dfree(x);
+  GUARD_END((PC) nullptr)
+  return 0;
 }
 
 }  // extern "C"

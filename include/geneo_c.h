@@ -470,6 +470,34 @@ PetscErrorCode GeneoTestCgSteps(GeneoSpmv h, int nsub, const int* suboff, int it
 long long GeneoTestCsrOp(int op, const GeneoCsr* A, const GeneoCsr* B, const int* iarg, const double* darg,
                          void* const* parg, int* rowptr_out, int* col_out, double* val_out, long long cap);
 
+/* A stand-alone multigrid hierarchy (test hook; host arrays in, host arrays out, no arithmetic in the hook).
+ * Create: A block diagonal with respect to suboff (nsub + 1 first rows, from 0 to A->n), uploaded by the hook and handed
+ * to the hierarchy as its resident level-0 matrix.  iparam = {coarse_size, smooth_degree, max_levels, single, max_m,
+ * setup, fine_companion}: setup 0 = sparse products on the device, 1 = host set-up + upload; fine_companion != 0 gives the
+ * level-0 matrix a single-precision companion of its owner's BEFORE the hierarchy borrows it.  dparam = {smooth_ratio,
+ * strength}.  The environment switches of the set-up (GENEO_AMG_*) are read as in a PC.  Returns 0, 1 on an error
+ * (PCGenEOGetError(NULL)), 2 when the device set-up declined (a row beyond the product kernels' capacity): nothing is
+ * built then and no fallback is taken. */
+typedef struct _p_GeneoTestAmg* GeneoTestAmg;
+int GeneoTestAmgCreate(const GeneoCsr* A, int nsub, const int* suboff, const int* iparam, const double* dparam,
+                       GeneoTestAmg* h);
+int GeneoTestAmgDestroy(GeneoTestAmg* h);
+int GeneoTestAmgInfo(GeneoTestAmg h, int* nlevels, double* operator_complexity, int* lp_matrices);
+/* One level.  iout[11] = {rows, nsub, fused, A.vec_lpr, A.nlong, companions, nnz A, nnz P, nnz R, nnz M, nnz Acs}: nnz -1
+ * = the level has no such matrix; companions: bit w set = matrix w (0 A, 1 P, 2 R, 3 M, 4 Acs) carries a
+ * single-precision companion.  suboff: nsub + 1, dinv: rows.  Any output may be NULL. */
+int GeneoTestAmgLevel(GeneoTestAmg h, int level, long long* iout, double* rho, int* suboff, double* dinv);
+/* CSR arrays of matrix `which` (0 A, 1 P, 2 R, 3 M = P - w D^-1 A P, 4 Acs = A diag(dinv)) of a level, as they lie in
+ * device memory.  Returns nnz (arrays filled when cap >= nnz; *rows its row count), -1: no such matrix, -2: error. */
+long long GeneoTestAmgMatrix(GeneoTestAmg h, int level, int which, int* rows, int* rowptr, int* col, double* val,
+                             long long cap);
+/* Dense inverses of the coarsest blocks: base[nsub + 1] element offsets, block s row-major at inv + base[s].  Returns
+ * base[nsub] (inv filled when cap allows), -2: error. */
+long long GeneoTestAmgCoarseInverse(GeneoTestAmg h, long long* base, double* inv, long long cap);
+/* X = V_level(B) (AmgDevice::vcycle_from): B rows x ldb, X rows x ldx, m columns used.  Both blocks are uploaded WHOLE,
+ * the cycle runs, and both are downloaded whole: padding columns of X and all of B come back as the device left them. */
+int GeneoTestAmgVcycle(GeneoTestAmg h, int level, double* B, int ldb, double* X, int ldx, int m);
+
 #ifdef __cplusplus
 }
 #endif
