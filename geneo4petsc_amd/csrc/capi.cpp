@@ -971,7 +971,7 @@ int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* co
       else if (k == "block_colscale") bk::block_colscale(c, d(1), I[1], I[2], d(2));
       else if (k == "cheb_dir")      // (GeneoSetKernelVariant("cheb_fused", 0): the composed form of core.cpp)
         rc = (geneo::cheb_fused() ? bk::cheb_dir(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6))
-                                  : geneo::cheb_dir_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6))) ? 1 : 0;
+                                  : geneo::cheb_dir_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), 1)) ? 1 : 0;
       else if (k == "block_init")
         bk::block_init(c, d(1), I[1], I[2], ip(2), ((uint64_t)(uint32_t)I[4] << 32) | (uint64_t)(uint32_t)I[3]);
       else if (k == "block_extract") bk::block_extract(c, d(1), I[1], I[2], d(2), ip(3), ip(4), lp(5), d(6));
@@ -1005,7 +1005,7 @@ int GeneoTestBlockPrimitive(const char* name, const int* I, const double* D, voi
       c = bk::chunks_upload(I[0], (const int*)P[0]);
       have_chunks = true;
       rc = (fused ? bk::cheb_dir_block(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), I[2])
-                  : geneo::cheb_dir_block_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), I[2])) ? 1 : 0;
+                  : geneo::cheb_dir_composed_once(c, d(1), I[1], d(2), d(3), d(4), d(5), d(6), I[2])) ? 1 : 0;
     } else if (k == "block_import") {
       rc = (fused ? bk::block_import(d(0), I[0], I[1], I[2], d(1), I[3])
                   : geneo::block_import_composed(d(0), I[0], I[1], I[2], d(1), I[3])) ? 1 : 0;

@@ -47,103 +47,27 @@ __attribute__((weak)) bool coarse_factor(const double*, int, int, double*, doubl
 __attribute__((weak)) bool coarse_solve(const double*, const double*, int, int, double*) { return false; }
 }  // namespace bk
 
-// The step kernel of the Chebyshev local solver (cheb_dev.h) composed of backend.h primitives: the definition a backend
-// without cheb_dev.hip links (the host twin), and on the GPU the comparison GeneoSetKernelVariant("cheb_fused", 0) selects.
+// The step of the Chebyshev local solver composed of backend.h primitives, at any width (w = 1: the vector step of
+// cheb_dev.h, w > 1: the slab step of block_dev.h): the definition a backend without those kernels links (the host twin),
+// and on the GPU the comparison GeneoSetKernelVariant("cheb_fused" | "block_fused", 0) selects.
 // d = fl(fl(a z) + fl(b d)): block_colscale rounds both products, axpy with factor 1 adds them with one rounding -- the
-// expression the fused kernel evaluates with contraction off.  Its scratch (ChebWork: one vector, the de-interleaved
-// coefficients and their gather indices) belongs to the caller: a PC allocates its own in setup_cheb and frees it in
-// cheb_release, so nothing is allocated inside a graph capture and nothing is shared between PCs.
+// expression the fused kernels evaluate with contraction off; block_rowscale(.., 1, 0, ..) stores the rounded product
+// d .* x and does not read its output.  The scratch (StepWork) belongs to the caller: a PC allocates its own before any
+// graph capture and frees it with the set-up, so nothing is allocated inside a capture and nothing is shared between PCs.
 namespace geneo {
-static std::atomic<int> g_cheb_fused{1};
+static std::atomic<int> g_cheb_fused{1}, g_block_fused{1};
 void set_cheb_fused(int on) { g_cheb_fused = on ? 1 : 0; }
 int cheb_fused() { return g_cheb_fused.load(); }
-
-void ChebWork::alloc(int n_, int ns_) {
-  release();
-  if (n_ <= 0 || ns_ <= 0) return;
-  t = (double*)bk::alloc(sizeof(double) * (size_t)n_);
-  ab = (double*)bk::alloc(sizeof(double) * 2 * (size_t)ns_);
-  idx = (int*)bk::alloc(sizeof(int) * 2 * (size_t)ns_);
-  std::vector<int> h(2 * (size_t)ns_);
-  for (int s = 0; s < ns_; ++s) {
-    h[s] = 2 * s;                // a_s ...
-    h[ns_ + s] = 2 * s + 1;      // ... then b_s
-  }
-  bk::h2d(idx, h.data(), sizeof(int) * h.size());
-  n = n_;
-  ns = ns_;
-}
-void ChebWork::release() {
-  bk::dfree(t);
-  bk::dfree(ab);
-  bk::dfree(idx);
-  t = ab = nullptr;
-  idx = nullptr;
-  n = ns = 0;
-}
-
-bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
-                       const double* dscale, double* out, const ChebWork& w) {
-  const int n = c.n, ns = c.nsub;
-  if (n <= 0 || ns <= 0) return true;
-  if (w.n < n || w.ns != ns) throw std::runtime_error("cheb_dir_composed: scratch of another size");
-  bk::gather(w.ab, coef_k, w.idx, ns);                  // a_0 .. a_{ns-1}
-  bk::gather(w.ab + ns, coef_k, w.idx + ns, ns);        // b_0 .. b_{ns-1}
-  if (flags & 1) {
-    bk::copy(d, z, n);
-    bk::block_colscale(c, d, 1, 1, w.ab);
-    bk::copy(x, d, n);
-  } else {
-    bk::copy(w.t, z, n);
-    bk::block_colscale(c, w.t, 1, 1, w.ab);
-    bk::block_colscale(c, d, 1, 1, w.ab + ns);
-    bk::axpy(d, 1.0, w.t, n);
-    bk::axpy(x, 1.0, d, n);
-  }
-  if (flags & 2) {
-    if (dscale) bk::xmy(out, x, dscale, n);
-    else bk::copy(out, x, n);
-  }
-  return true;
-}
-
-// one call with scratch of its own (the weak bk::cheb_dir below and the primitive test): allocates, runs, waits, frees
-bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
-                            const double* dscale, double* out) {
-  struct Own {
-    ChebWork w;
-    ~Own() { w.release(); }
-  } own;
-  own.w.alloc(c.n, c.nsub);
-  const bool ok = cheb_dir_composed(c, coef_k, flags, z, d, x, dscale, out, own.w);
-  bk::sync();
-  return ok;
-}
-}  // namespace geneo
-
-namespace bk {
-__attribute__((weak)) bool cheb_dir(const Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
-                                    const double* dscale, double* out) {
-  return geneo::cheb_dir_composed_once(c, coef_k, flags, z, d, x, dscale, out);
-}
-__attribute__((weak)) bool cheb_residual(const Csr&, const double*, const double*, double*) { return false; }
-}  // namespace bk
-
-// The operations of the block entry points (block_dev.h) composed of backend.h primitives: what a backend without
-// block_dev.hip links (the host twin), and on the GPU the comparison GeneoSetKernelVariant("block_fused", 0) selects.
-// Products and sums are rounded one by one, as the kernels do: block_colscale stores the rounded product, axpy with factor
-// 1 adds with one rounding; copies of columns go through block_axpby(.., 1, .., 0, ..), which moves bits.
-namespace geneo {
-static std::atomic<int> g_block_fused{1};
 void set_block_fused(int on) { g_block_fused = on ? 1 : 0; }
 int block_fused() { return g_block_fused.load(); }
+static int step_fused(int w) { return w == 1 ? g_cheb_fused.load() : g_block_fused.load(); }
 
 static int slab_entries(int n, int w) {
   if ((int64_t)n * w > 0x7fffffffll) throw std::runtime_error("GenEO: a slab of right-hand sides exceeds 2^31 entries");
   return n * w;
 }
 
-void BlockWork::alloc(int n_, int ns_, int w_) {
+void StepWork::alloc(int n_, int ns_, int w_) {
   release();
   if (n_ <= 0 || ns_ <= 0 || w_ <= 0) return;
   t = (double*)bk::alloc(sizeof(double) * (size_t)n_ * w_);
@@ -160,7 +84,7 @@ void BlockWork::alloc(int n_, int ns_, int w_) {
   ns = ns_;
   w = w_;
 }
-void BlockWork::release() {
+void StepWork::release() {
   bk::dfree(t);
   bk::dfree(ab);
   bk::dfree(idx);
@@ -169,11 +93,11 @@ void BlockWork::release() {
   n = ns = w = 0;
 }
 
-bool cheb_dir_block_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
-                             const double* dscale, double* Out, int w, const BlockWork& wk) {
+bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                       const double* dscale, double* Out, int w, const StepWork& wk) {
   const int n = c.n, ns = c.nsub;
   if (n <= 0 || ns <= 0) return true;
-  if (wk.n < n || wk.ns != ns || wk.w != w) throw std::runtime_error("cheb_dir_block_composed: scratch of another size");
+  if (wk.n < n || wk.ns != ns || wk.w != w) throw std::runtime_error("cheb_dir_composed: scratch of another size");
   const int nw = slab_entries(n, w);
   bk::gather(wk.ab, coef_k, wk.idx, 2 * ns * w);
   if (flags & 1) {
@@ -194,18 +118,22 @@ bool cheb_dir_block_composed(const bk::Chunks& c, const double* coef_k, int flag
   return true;
 }
 
-bool cheb_dir_block_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
-                                  const double* dscale, double* Out, int w) {
+// one call with scratch of its own (the weak bk::cheb_dir / bk::cheb_dir_block below and the primitive tests):
+// allocates, runs, waits, frees
+bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                            const double* dscale, double* Out, int w) {
   struct Own {
-    BlockWork w;
+    StepWork w;
     ~Own() { w.release(); }
   } own;
   own.w.alloc(c.n, c.nsub, w);
-  const bool ok = cheb_dir_block_composed(c, coef_k, flags, Z, D, X, dscale, Out, w, own.w);
+  const bool ok = cheb_dir_composed(c, coef_k, flags, Z, D, X, dscale, Out, w, own.w);
   bk::sync();
   return ok;
 }
 
+// The other operations of the block entry points (block_dev.h), composed in the same way: products and sums are rounded
+// one by one, as the kernels do; copies of columns go through block_axpby(.., 1, .., 0, ..), which moves bits.
 bool block_import_composed(const double* Xcm, int ld, int n, int m, double* Yrm, int w) {
   if (n <= 0) return true;
   bk::zero(Yrm, sizeof(double) * (size_t)n * w);
@@ -287,9 +215,14 @@ bool chol_solve_block_composed_once(const double* L, const double* LT, int n, do
 }  // namespace geneo
 
 namespace bk {
+__attribute__((weak)) bool cheb_dir(const Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
+                                    const double* dscale, double* out) {
+  return geneo::cheb_dir_composed_once(c, coef_k, flags, z, d, x, dscale, out, 1);
+}
+__attribute__((weak)) bool cheb_residual(const Csr&, const double*, const double*, double*) { return false; }
 __attribute__((weak)) bool cheb_dir_block(const Chunks& c, const double* coef_k, int flags, const double* Z, double* D,
                                           double* X, const double* dscale, double* Out, int w) {
-  return geneo::cheb_dir_block_composed_once(c, coef_k, flags, Z, D, X, dscale, Out, w);
+  return geneo::cheb_dir_composed_once(c, coef_k, flags, Z, D, X, dscale, Out, w);
 }
 __attribute__((weak)) bool block_import(const double* Xcm, int ld, int n, int m, double* Yrm, int w) {
   return geneo::block_import_composed(Xcm, ld, n, m, Yrm, w);
@@ -760,6 +693,13 @@ int PC::build_layout() {
   d_xe = dv(nE); d_ye = dv(nE); d_xL = dv(nL); d_wL = dv(nL);
   d_cg_r = dv(nL); d_cg_z = dv(nL); d_cg_p = dv(nL); d_cg_q = dv(nL); d_cg_sc = dv((size_t)8 * std::max(1, ns));
   d_t1 = dv(nown); d_t2 = dv(nown); d_t3 = dv(nown); d_x0 = dv(nown); d_scal = dv(16);
+  vec.w = 1;
+  vec.coarse = true;
+  vec.wl = d_wL; vec.xl = d_xL; vec.r1 = d_cg_r; vec.z = d_cg_z; vec.d = d_cg_p;
+  vec.t1 = d_t1; vec.t2 = d_t2; vec.t3 = d_t3;
+  vec.xe = d_xe; vec.ye = d_ye;
+  vec.work = &cheb_work;
+  vec.chain = &cheb_chain;
   return 0;
 }
 
@@ -1395,6 +1335,56 @@ int PC::setup_finish(const double* b_dev) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------ HIP graphs
+// Records the launches of `body` into a graph: recorded, not run.  Null, and `failed` set for good, when the backend
+// cannot capture; a body that throws leaves the capture cleanly (the stream and the capture flag are global state).
+template <class Body>
+static void* capture_graph(bool& failed, Body&& body) {
+  if (failed || !bk::graph_capture_begin()) {
+    failed = true;
+    return nullptr;
+  }
+  try {
+    body();
+  } catch (...) {
+    bk::graph_capture_end();
+    failed = true;
+    throw;
+  }
+  void* g = bk::graph_capture_end();
+  if (!g) failed = true;
+  return g;
+}
+
+// One run of a chain that is one linear sequence of launches on one stream and allocates nothing: the first run records
+// the graph and goes out as direct launches, later runs replay it.  While bench.py's in-situ kernel timer runs, every 8th
+// run is launched directly so that its kernels are sampled (HIP events cannot bracket kernels inside a replayed graph).
+template <class Body>
+int PC::Replay::run(const void* buf_, int fused_, Body&& body) {
+  if (graph && (buf != buf_ || fused != fused_)) {
+    bk::graph_destroy(graph);
+    graph = nullptr;
+  }
+  bool direct = false;
+  if (!graph) {
+    direct = true;
+    graph = capture_graph(failed, [&] { value = body(); });
+    buf = buf_;
+    fused = fused_;
+  } else if (bk::spmv_profiling() && (runs % 8 == 0)) {
+    direct = true;
+  }
+  ++runs;
+  if (direct) return body();
+  bk::graph_launch(graph);
+  ++replays;
+  return value;
+}
+void PC::Replay::reset() {
+  if (graph) bk::graph_destroy(graph);
+  *this = Replay{};
+}
+
 // ------------------------------------------------------------------------------------ R, R^T, comm
 void PC::allreduce(double* dev, int n) {
   if (size == 1 || n == 0) return;
@@ -1406,100 +1396,78 @@ void PC::allreduce(double* dev, int n) {
   }
 }
 
-void PC::restrict_to_local(const double* x, double* xL) {
+// R, sum R^T and A on w vectors (w > 1: row-major blocks, as the blocked assembly of E and the block entry points use
+// them).  The single-vector forms of the three primitives are taken at w == 1, here and nowhere else.  At w > 1 the halo
+// buffers hold comm_width x the single-vector counts, and the exchange callback gets the width in the upper bits of its
+// flag (flag = reverse | width << 1); at w == 1 the flag is the plain `reverse`.
+static void gather_w(double* dst, const double* src, const int* idx, int n, int w) {
+  if (w == 1) bk::gather(dst, src, idx, n);
+  else bk::gather_rows(dst, src, idx, n, w);
+}
+static void segsum_w(double* y, const double* v, const int* ptr, const int* idx, int n, int w, bool add) {
+  if (w == 1) bk::segsum(y, v, ptr, idx, n, add);
+  else bk::segsum_rows(y, v, ptr, idx, n, w, add);
+}
+static void spmv_w(const bk::Csr& A, const double* X, double* Y, int w) {
+  if (w == 1) bk::spmv(A, X, Y);
+  else bk::spmm_strided(A, X, w, Y, w, w, nullptr, nullptr);
+}
+static int exchange_flag(int reverse, int w) { return w == 1 ? reverse : reverse | (w << 1); }
+
+void PC::restrict(const double* X, double* XL, int w, double* xe) {
   if (size == 1) {
-    bk::gather(xL, x, d_l2e, nL);
+    gather_w(XL, X, d_l2e, nL, w);
     return;
   }
   const int nown = n_owned();
-  bk::gather(comm_send, x, d_send_idx, (int)send_idx.size());
-  if (cb_exchange(cb_user, 0)) throw std::runtime_error("GenEO: halo exchange callback failed");
-  bk::copy(d_xe, x, nown);
-  bk::copy(d_xe + nown, comm_recv, nH);
-  bk::gather(xL, d_xe, d_l2e, nL);
+  gather_w(comm_send, X, d_send_idx, (int)send_idx.size(), w);
+  if (cb_exchange(cb_user, exchange_flag(0, w))) throw std::runtime_error("GenEO: halo exchange callback failed");
+  bk::copy(xe, X, (int)((int64_t)nown * w));
+  bk::copy(xe + (int64_t)nown * w, comm_recv, (int)((int64_t)nH * w));
+  gather_w(XL, xe, d_l2e, nL, w);
 }
 
-void PC::prolong_add(const double* wL, double* y) {
+void PC::prolong(const double* WL, double* Y, int w, double* ye) {
   const int nown = n_owned();
   if (size == 1) {
-    bk::segsum(y, wL, d_rt_ptr, d_rt_idx, nown, false);
+    segsum_w(Y, WL, d_rt_ptr, d_rt_idx, nown, w, false);
     return;
   }
-  bk::segsum(d_ye, wL, d_rt_ptr, d_rt_idx, nE, false);
-  bk::copy(comm_send, d_ye + nown, nH);
-  if (cb_exchange(cb_user, 1)) throw std::runtime_error("GenEO: halo exchange callback failed");
-  bk::copy(y, d_ye, nown);
-  bk::segsum(y, comm_recv, d_rv_ptr, d_rv_idx, nown, true);
+  segsum_w(ye, WL, d_rt_ptr, d_rt_idx, nE, w, false);
+  bk::copy(comm_send, ye + (int64_t)nown * w, (int)((int64_t)nH * w));
+  if (cb_exchange(cb_user, exchange_flag(1, w))) throw std::runtime_error("GenEO: halo exchange callback failed");
+  bk::copy(Y, ye, (int)((int64_t)nown * w));
+  segsum_w(Y, comm_recv, d_rv_ptr, d_rv_idx, nown, w, true);
+}
+
+void PC::matmult(const double* X, double* Y, int w, double* WL, double* xe, double* ye) {
+  info.spmv_calls += w;
+  if (size == 1) {
+    spmv_w(neuE, X, WL, w);
+  } else {
+    const int nown = n_owned();
+    gather_w(comm_send, X, d_send_idx, (int)send_idx.size(), w);
+    if (cb_exchange(cb_user, exchange_flag(0, w))) throw std::runtime_error("GenEO: halo exchange callback failed");
+    bk::copy(xe, X, (int)((int64_t)nown * w));
+    bk::copy(xe + (int64_t)nown * w, comm_recv, (int)((int64_t)nH * w));
+    spmv_w(neuE, xe, WL, w);
+  }
+  prolong(WL, Y, w, ye);
 }
 
 int PC::matmult(const double* x, double* y) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
-  info.spmv_calls++;
-  if (size == 1) {
-    bk::spmv(neuE, x, d_wL);
-  } else {
-    const int nown = n_owned();
-    bk::gather(comm_send, x, d_send_idx, (int)send_idx.size());
-    if (cb_exchange(cb_user, 0)) return fail("GenEO: halo exchange callback failed");
-    bk::copy(d_xe, x, nown);
-    bk::copy(d_xe + nown, comm_recv, nH);
-    bk::spmv(neuE, d_xe, d_wL);
+  try {
+    matmult(x, y, 1, d_wL, d_xe, d_ye);
+  } catch (std::exception& e) {
+    return fail(e.what());
   }
-  prolong_add(d_wL, y);
   return 0;
-}
-
-// ---- the same three operators on row-major blocks of w vectors (blocked assembly of E) ----------------
-// The halo buffers hold comm_width x the single-vector counts; the exchange callback gets the width in
-// the upper bits of its flag (flag = reverse | width << 1).
-void PC::restrict_block(const double* X, double* XL, int w, double* xe) {
-  if (size == 1) {
-    bk::gather_rows(XL, X, d_l2e, nL, w);
-    return;
-  }
-  const int nown = n_owned();
-  bk::gather_rows(comm_send, X, d_send_idx, (int)send_idx.size(), w);
-  if (cb_exchange(cb_user, 0 | (w << 1))) throw std::runtime_error("GenEO: halo exchange callback failed");
-  bk::copy(xe, X, (int)((int64_t)nown * w));
-  bk::copy(xe + (int64_t)nown * w, comm_recv, (int)((int64_t)nH * w));
-  bk::gather_rows(XL, xe, d_l2e, nL, w);
-}
-
-void PC::prolong_block(const double* WL, double* Y, int w, double* ye) {
-  const int nown = n_owned();
-  if (size == 1) {
-    bk::segsum_rows(Y, WL, d_rt_ptr, d_rt_idx, nown, w, false);
-    return;
-  }
-  bk::segsum_rows(ye, WL, d_rt_ptr, d_rt_idx, nE, w, false);
-  bk::copy(comm_send, ye + (int64_t)nown * w, (int)((int64_t)nH * w));
-  if (cb_exchange(cb_user, 1 | (w << 1))) throw std::runtime_error("GenEO: halo exchange callback failed");
-  bk::copy(Y, ye, (int)((int64_t)nown * w));
-  bk::segsum_rows(Y, comm_recv, d_rv_ptr, d_rv_idx, nown, w, true);
-}
-
-void PC::matmult_block(const double* X, double* Y, int w, double* WL, double* xe) {
-  info.spmv_calls += w;
-  if (size == 1) {
-    bk::spmm_strided(neuE, X, w, WL, w, w, nullptr, nullptr);
-  } else {
-    const int nown = n_owned();
-    bk::gather_rows(comm_send, X, d_send_idx, (int)send_idx.size(), w);
-    if (cb_exchange(cb_user, 0 | (w << 1))) throw std::runtime_error("GenEO: halo exchange callback failed");
-    bk::copy(xe, X, (int)((int64_t)nown * w));
-    bk::copy(xe + (int64_t)nown * w, comm_recv, (int)((int64_t)nH * w));
-    bk::spmm_strided(neuE, xe, w, WL, w, w, nullptr, nullptr);
-  }
-  prolong_block(WL, Y, w, xe);
 }
 
 // [D] M^-1 [D] on the concatenated local space: one independent Jacobi-PCG per subdomain,
 // all subdomains advanced by the same launches (geneo.cpp:1991-2002 with MUMPS replaced).
-void PC::local_solve(double* wL) {
-  if (opt.dls1_ksp == "chebyshev") {
-    local_solve_cheb(wL);
-    return;
-  }
+void PC::local_solve_cg(double* wL) {
   if (opt.lvl1RAS) bk::xmy(wL, wL, d_D, nL);
   const int ns = (int)subs.size();
   const bool use_amg = (opt.dls1_pc == "amg") && amg1;
@@ -1543,21 +1511,10 @@ void PC::local_solve(double* wL) {
     const int key = 2 * len + parity;
     auto it_g = cg_graphs.find(key);
     if (it_g != cg_graphs.end()) return it_g->second;
-    void* g = nullptr;
     const int parity_in = parity;
-    if (bk::graph_capture_begin()) {
-      try {
-        chunk(len);
-      } catch (...) {       // leave the capture cleanly (the stream and the capture flag are global state)
-        bk::graph_capture_end();
-        cg_graph_failed = true;
-        throw;
-      }
-      g = bk::graph_capture_end();
-      parity = parity_in;        // recorded, not run
-    }
-    if (!g) cg_graph_failed = true;
-    else cg_graphs[key] = g;
+    void* g = capture_graph(cg_graph_failed, [&] { chunk(len); });
+    parity = parity_in;        // recorded, not run
+    if (g) cg_graphs[key] = g;
     return g;
   };
   static const bool dbg_dls1 = getenv("GENEO_DEBUG_DLS1") != nullptr;   // per solve: the chunk boundary each subdomain froze at
@@ -1627,18 +1584,12 @@ void PC::local_solve(double* wL) {
 // A fixed linear operator, symmetric whenever V is and positive definite as long as hi_s bounds the spectrum of V A
 // from above, whatever -dls1_ksp_rtol: no reductions, no host polling, one chain of launches of known length.
 void PC::cheb_release() {
-  if (cheb_graph) bk::graph_destroy(cheb_graph);
-  cheb_graph = nullptr;
-  cheb_graph_failed = false;
-  cheb_graph_wL = nullptr;
-  cheb_graph_fused = -1;
+  cheb_chain.reset();
   bk::dfree(d_cheb_coef);
   d_cheb_coef = nullptr;
   cheb_work.release();
   cheb_K = 0;
-  cheb_solves = 0;
-  cheb_graph_launches = cheb_res_fused = 0;
-  cheb_graph_res = 0;
+  cheb_res_fused = 0;
   cheb_lo.clear();
   cheb_hi.clear();
   cheb_achieved.clear();
@@ -1675,7 +1626,7 @@ int PC::setup_cheb() {
   cheb_release();
   const int ns = (int)subs.size();
   if (!amg1) return fail("GenEO preconditioner: -dls1_ksp_type chebyshev needs the level-1 hierarchy (-dls1_pc_type amg)");
-  if (ns == 0 || nL == 0) return 0;      // a rank without rows: local_solve_cheb has nothing to do there either
+  if (ns == 0 || nL == 0) return 0;      // a rank without rows: local_solve has nothing to do there either
   const int nlz = opt.dls1_cheb_esteig_its;
   if (!(opt.dls1_cheb_safety_lo > 0.0) || !(opt.dls1_cheb_safety_hi > 0.0))
     return fail("GenEO preconditioner: -dls1_cheb_safety needs two positive factors");
@@ -1761,11 +1712,11 @@ int PC::setup_cheb() {
   d_cheb_coef = (double*)bk::alloc(sizeof(double) * coef.size());
   bk::h2d(d_cheb_coef, coef.data(), sizeof(double) * coef.size());
   cheb_K = K;
-  cheb_work.alloc(nL, ns);
+  cheb_work.alloc(nL, ns, 1);
   // Verification: one solve on the estimation right-hand side (no partition-of-unity scalings), ||b - A x|| / ||b|| per
   // subdomain.  At or above 1 the polynomial grew: the upper bound lies below the spectrum.
   bk::copy(d_wL, tmp.rhs, nL);
-  cheb_steps(d_wL, nullptr);
+  cheb_steps(vec, nullptr);
   bk::spmv(dirL, d_wL, d_cg_q);
   bk::axpy(d_cg_q, -1.0, tmp.rhs, nL);
   bk::seg_dot(ch, d_cg_q, d_cg_q, tmp.nrm, 2, 0);
@@ -1789,81 +1740,78 @@ int PC::setup_cheb() {
   return 0;
 }
 
-// The K steps: wL holds b on entry and x (dscale .* x) on return.  The residual travels between wL and d_cg_r (the fused
-// residual kernel writes out of place); the direction lives in d_cg_p, the solution in d_xL.
-int PC::cheb_steps(double* wL, const double* dscale) {
-  const int ns = (int)subs.size(), K = cheb_K;
-  const bool fused = g_cheb_fused.load() != 0;
-  const bool fusable = fused && bk::csr_fusable(dirL);
-  double *rc = wL, *ro = d_cg_r;
+// The K steps on a.wl, which holds b on entry and x (dscale .* x) on return.  The residual travels between a.wl and a.r1
+// (the fused residual kernel and the residual epilogue of the SpMM write out of place); the direction lives in a.d, the
+// solution in a.xl.  The vector residual update is bk::cheb_residual where the matrix allows it (counted), otherwise SpMV
+// and axpy; the slab's is the SpMM with its residual epilogue.
+int PC::cheb_steps(const App& a, const double* dscale) {
+  const int ns = (int)subs.size(), K = cheb_K, w = a.w;
+  const bool fused = step_fused(w) != 0;
+  const bool fusable = w == 1 && fused && bk::csr_fusable(dirL);
+  double *rc = a.wl, *ro = a.r1;
   int nres = 0;
   for (int k = 0; k < K; ++k) {
-    amg1->vcycle(rc, 1, d_cg_z, 1, 1);
+    amg1->vcycle(rc, w, a.z, w, w);
     const int flags = (k == 0 ? 1 : 0) | (k == K - 1 ? 2 : 0);
     const double* ck = d_cheb_coef + (size_t)k * ns * 2;
-    if (fused) bk::cheb_dir(ch, ck, flags, d_cg_z, d_cg_p, d_xL, dscale, wL);
-    else cheb_dir_composed(ch, ck, flags, d_cg_z, d_cg_p, d_xL, dscale, wL, cheb_work);
+    if (!fused) cheb_dir_composed(ch, ck, flags, a.z, a.d, a.xl, dscale, a.wl, w, *a.work);
+    else if (w == 1) bk::cheb_dir(ch, ck, flags, a.z, a.d, a.xl, dscale, a.wl);
+    else bk::cheb_dir_block(ch, ck, flags, a.z, a.d, a.xl, dscale, a.wl, w);
     if (k == K - 1) break;
-    if (fusable && bk::cheb_residual(dirL, d_cg_p, rc, ro)) {
+    if (w > 1) {
+      bk::spmm_fused(dirL, bk::EPI_RES, a.d, w, ro, w, w, rc, w, nullptr, 0, nullptr, 0.0);   // r_out = r_in - A d
+      std::swap(rc, ro);
+    } else if (fusable && bk::cheb_residual(dirL, a.d, rc, ro)) {
       std::swap(rc, ro);
       ++nres;
     } else {
-      bk::spmv(dirL, d_cg_p, d_cg_q);
+      bk::spmv(dirL, a.d, d_cg_q);
       bk::axpy(rc, -1.0, d_cg_q, nL);
     }
   }
   return nres;
 }
 
-void PC::local_solve_cheb(double* wL) {
+// [D] M^-1 [D] on a.wl.  The vector instance takes the solver -dls1_ksp_type names; a slab has the Chebyshev chain alone
+// (setup_block), the same fixed linear operator for every column.  The chain is captured once per set-up and width into a
+// HIP graph (Replay::run).
+void PC::local_solve(const App& a) {
+  const int w = a.w;
+  if (w == 1 && opt.dls1_ksp != "chebyshev") {
+    local_solve_cg(a.wl);
+    return;
+  }
   if (nL == 0 || subs.empty()) return;   // a rank without rows (setup_cheb made no table for it)
   if (!d_cheb_coef || cheb_K <= 0 || !amg1) throw std::runtime_error("GenEO - solve KO: dls1 (-dls1_ksp_type chebyshev was not set up)");
-  if (opt.lvl1RAS) bk::xmy(wL, wL, d_D, nL);
+  if (opt.lvl1RAS) {
+    if (w == 1) bk::xmy(a.wl, a.wl, d_D, nL);
+    else bk::block_rowscale(a.wl, w, a.wl, w, d_D, 1.0, 0.0, nL, w);
+  }
   const double* dscale = opt.lvl1SRAS ? d_D : nullptr;
-  // The whole solve is one linear chain of launches on one stream: captured once per PC into a HIP graph (recorded, not
-  // run, by the first solve, which goes out as direct launches) and replayed from the second solve on.  While bench.py's
-  // in-situ kernel timer runs, every 8th solve is launched directly so that its kernels are sampled, as the PCG path does.
-  const int fused = g_cheb_fused.load();
-  if (cheb_graph && (cheb_graph_wL != wL || cheb_graph_fused != fused)) {
-    bk::graph_destroy(cheb_graph);
-    cheb_graph = nullptr;
-  }
-  bool direct = false;
-  if (!cheb_graph) {
-    direct = true;
-    if (!cheb_graph_failed && bk::graph_capture_begin()) {
-      try {
-        cheb_graph_res = cheb_steps(wL, dscale);
-      } catch (...) {
-        bk::graph_capture_end();
-        cheb_graph_failed = true;
-        throw;
-      }
-      cheb_graph = bk::graph_capture_end();
-      cheb_graph_wL = wL;
-      cheb_graph_fused = fused;
-      if (!cheb_graph) cheb_graph_failed = true;
-    } else {
-      cheb_graph_failed = true;
-    }
-  } else if (bk::spmv_profiling() && (cheb_solves % 8 == 0)) {
-    direct = true;
-  }
-  ++cheb_solves;
-  if (direct) {
-    cheb_res_fused += cheb_steps(wL, dscale);
-  } else {
-    bk::graph_launch(cheb_graph);
-    ++cheb_graph_launches;
-    cheb_res_fused += cheb_graph_res;
-  }
-  info.dls1_iterations += cheb_K;
+  const int fused = step_fused(w);
+  if (!fused && !a.work->t) a.work->alloc(nL, (int)subs.size(), w);     // (before any capture: nothing is allocated inside one)
+  const int nres = a.chain->run(a.wl, fused, [&] { return cheb_steps(a, dscale); });
+  if (w == 1) cheb_res_fused += nres;
+  info.dls1_iterations += cheb_K;     // one chain of K steps, whatever the width
   info.dls1_solves += 1;
 }
 
-// yE <- E^-1 yE by the path of the factor this set-up made (see coarse_solve_local)
-void PC::coarse_einv(double* yE) {
-  if (E_dev) {
+// yE <- E^-1 yE on w coarse vectors (w > 1: the dimE x w row-major block) by the path of the factor this set-up made (see
+// coarse_solve).  A block with a host-made Cholesky factor on the device (dimE <= 1024): one launch for all columns;
+// otherwise column by column through the single-vector path.
+void PC::coarse_einv(double* yE, int w) {
+  if (w > 1) {
+    if (!E_dev && E_chol && d_EL && dimE <= 1024) {
+      const bool ok = g_block_fused.load() ? bk::chol_solve_block(d_EL, d_ELT, dimE, yE, w)
+                                           : chol_solve_block_composed_once(d_EL, d_ELT, dimE, yE, w);
+      if (ok) return;
+    }
+    for (int j = 0; j < w; ++j) {
+      bk::block_axpby(blk_col, 1, 1.0, yE + j, w, 0.0, dimE, 1);
+      coarse_einv(blk_col, 1);
+      bk::block_axpby(yE + j, w, 1.0, blk_col, 1, 0.0, dimE, 1);
+    }
+  } else if (E_dev) {
     if (!bk::coarse_solve(d_EL, d_ELT, dimE, E_nb, yE)) throw std::runtime_error("GenEO - solve KO: dcs2 (no blocked coarse sweeps on this backend)");
   } else if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
     bk::d2h(h_yE.data(), yE, sizeof(double) * dimE);
@@ -1873,29 +1821,99 @@ void PC::coarse_einv(double* yE) {
   }
 }
 
-// yE = E^-1 Z^T x, Z^T x taken from the already restricted xL; replicated host solve
-void PC::coarse_solve_local(const double* xL, double* yE) {
+// The coarse coefficients E^-1 Z^T x, Z^T x taken from the already restricted XL.  Vector: d_yE, through zt_apply on the
+// column-major Z.  Slab: blk_C[s] (kp x w) = the rows that belong to subdomain s, through the Gram kernel on the row-major
+// blk_ZR and row gathers between Gram rows, the replicated coarse block and coefficient rows.
+void PC::coarse_solve(const App& a, const double* XL) {
+  const int w = a.w;
+  double* yE = w == 1 ? d_yE : blk_yE;
   auto t0 = clk::now();
-  bk::zt_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, kmax, xL, yE, dimE);
-  allreduce(yE, dimE);
+  if (w == 1) {
+    bk::zt_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, kmax, XL, yE, dimE);
+  } else {
+    bk::gram(ch, blk_ZR, blk_kp, blk_kp, XL, w, w, blk_G);
+    bk::gather_rows(yE, blk_G, blk_g2e, dimE, w);
+  }
+  allreduce(yE, slab_entries(dimE, w));
   auto t1 = clk::now();
   // E^-1 (geneo.cpp:1493, KSPSolve(pcKSPL2)): the replicated Cholesky factor lives on the device and the two triangular
   // sweeps are one launch behind the all-reduce -- no download, host solve, upload and no host synchronisation in the
   // preconditioner application.  A factor made on the device (build_E) takes the blocked sweeps, at any dimE, stream-ordered
   // in the same way.  Host path: E not positive definite to rounding (LU with pivoting), or dimE > 1024 with a host factor.
-  coarse_einv(yE);
-  auto t2 = clk::now();
+  coarse_einv(yE, w);
+  if (w > 1) bk::gather_rows(blk_C, yE, blk_e2c, (int)subs.size() * blk_kp, w);
   info.lvl2ApplyZtTimeLoc += secs(t0, t1);
-  info.lvl2ApplyEinvTimeLoc += secs(t1, t2);
+  info.lvl2ApplyEinvTimeLoc += secs(t1, clk::now());
+}
+
+// WL = Z c (add: WL += Z c) with the coefficients coarse_solve left
+void PC::coarse_expand(const App& a, double* WL, bool add) {
+  if (a.w == 1) bk::z_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, d_yE, WL, add);
+  else bk::block_mul(ch, blk_ZR, blk_kp, blk_kp, blk_C, a.w, WL, a.w, add);
+}
+
+// Q = sum R^T Z E^-1 Z^T R (applyQ, geneo.cpp:1435); an empty coarse space: Q = 0
+void PC::apply_q_on(const App& a, const double* X, double* Y) {
+  if (!a.coarse) {
+    bk::zero(Y, sizeof(double) * (size_t)n_owned() * a.w);
+    return;
+  }
+  restrict(X, a.xl, a.w, a.xe);
+  coarse_solve(a, a.xl);
+  coarse_expand(a, a.wl, false);
+  prolong(a.wl, Y, a.w, a.ye);
+}
+
+void PC::apply_on(const App& a, const double* X, double* Y) {
+  const int w = a.w, nw = slab_entries(n_owned(), w);
+  auto t0 = clk::now();
+  if (opt.lvl2 && !opt.hybrid) {
+    // y = sum R^T ( Z_s E^-1 Z^T x + [D] M^-1 [D] R x ): one restriction, one prolongation
+    restrict(X, a.wl, w, a.xe);
+    if (a.coarse) coarse_solve(a, a.wl);
+    auto t1 = clk::now();
+    local_solve(a);
+    auto t2 = clk::now();
+    if (a.coarse) coarse_expand(a, a.wl, true);
+    prolong(a.wl, Y, w, a.ye);
+    info.lvl2ApplyTimeLoc += secs(t0, t1);
+    info.lvl1ApplyMinvTimeLoc += secs(t1, t2);
+    info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+    return;
+  }
+  // generic composition (geneo.cpp:2074-2094)
+  bool have_q = false;
+  if (opt.lvl2 && !opt.effHybrid) {  // applyLevel2
+    apply_q_on(a, X, Y);
+    have_q = true;
+    info.lvl2ApplyTimeLoc += secs(t0, clk::now());
+  }
+  auto t1 = clk::now();
+  double* W = a.t1;
+  bk::copy(W, X, nw);
+  if (opt.hybrid && !opt.effHybrid) {  // (I - P^T): w = x - A (Q x), geneo.cpp:1931,1944
+    matmult(Y, a.t2, w, a.wl, a.xe, a.ye);
+    bk::axpy(W, -1.0, a.t2, nw);
+  }
+  restrict(W, a.wl, w, a.xe);
+  auto t2 = clk::now();
+  local_solve(a);
+  info.lvl1ApplyMinvTimeLoc += secs(t2, clk::now());
+  prolong(a.wl, W, w, a.ye);
+  if (opt.hybrid) {  // (I - P): w = w - Q (A w), geneo.cpp:1935-1944
+    matmult(W, a.t2, w, a.wl, a.xe, a.ye);
+    apply_q_on(a, a.t2, a.t3);
+    bk::axpy(W, -1.0, a.t3, nw);
+  }
+  if (have_q) bk::axpy(Y, 1.0, W, nw);
+  else bk::copy(Y, W, nw);
+  info.lvl1ApplyTimeLoc += secs(t1, clk::now());
 }
 
 int PC::apply_q(const double* x, double* y) {
   if (!is_setup || !opt.lvl2) return fail("GenEO preconditioner: no coarse space");
   try {
-    restrict_to_local(x, d_xL);
-    coarse_solve_local(d_xL, d_yE);
-    bk::z_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, d_yE, d_wL, false);
-    prolong_add(d_wL, y);
+    apply_q_on(vec, x, y);
   } catch (std::exception& e) {
     return fail(e.what());
   }
@@ -1904,50 +1922,8 @@ int PC::apply_q(const double* x, double* y) {
 
 int PC::apply(const double* x, double* y) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
-  const int nown = n_owned();
   try {
-    auto t0 = clk::now();
-    if (opt.lvl2 && !opt.hybrid) {
-      // y = sum R^T ( Z_s E^-1 Z^T x + [D] M^-1 [D] R x ): one restriction, one prolongation
-      restrict_to_local(x, d_wL);
-      coarse_solve_local(d_wL, d_yE);
-      auto t1 = clk::now();
-      local_solve(d_wL);
-      auto t2 = clk::now();
-      bk::z_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, d_yE, d_wL, true);
-      prolong_add(d_wL, y);
-      info.lvl2ApplyTimeLoc += secs(t0, t1);
-      info.lvl1ApplyMinvTimeLoc += secs(t1, t2);
-      info.lvl1ApplyTimeLoc += secs(t1, clk::now());
-      return 0;
-    }
-    // generic composition (geneo.cpp:2074-2094)
-    bool have_q = false;
-    if (opt.lvl2 && !opt.effHybrid) {  // applyLevel2
-      if (int rc = apply_q(x, y)) return rc;
-      have_q = true;
-      info.lvl2ApplyTimeLoc += secs(t0, clk::now());
-    }
-    auto t1 = clk::now();
-    double* w = d_t1;
-    bk::copy(w, x, nown);
-    if (opt.hybrid && !opt.effHybrid) {  // (I - P^T): w = x - A (Q x), geneo.cpp:1931,1944
-      if (int rc = matmult(y, d_t2)) return rc;
-      bk::axpy(w, -1.0, d_t2, nown);
-    }
-    restrict_to_local(w, d_wL);
-    auto t2 = clk::now();
-    local_solve(d_wL);
-    info.lvl1ApplyMinvTimeLoc += secs(t2, clk::now());
-    prolong_add(d_wL, w);
-    if (opt.hybrid) {  // (I - P): w = w - Q (A w), geneo.cpp:1935-1944
-      if (int rc = matmult(w, d_t2)) return rc;
-      if (int rc = apply_q(d_t2, d_t3)) return rc;
-      bk::axpy(w, -1.0, d_t3, nown);
-    }
-    if (have_q) bk::axpy(y, 1.0, w, nown);
-    else bk::copy(y, w, nown);
-    info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+    apply_on(vec, x, y);
   } catch (std::exception& e) {
     return fail(e.what());
   }
@@ -1955,16 +1931,14 @@ int PC::apply(const double* x, double* y) {
 }
 
 // ---- blocks of right-hand sides (-geneo_block_width 16 | 32; PCMatApply_GenEO, MatMatMult_GenEO, KSPMatSolve_GenEO) ----
-// Slabs of w columns, row-major, through the block forms of the restriction, the prolongation and the operator that the
-// assembly of E uses, the V-cycle on blocks that LOBPCG uses, and the kernels of block_dev.h.  With the Chebyshev local
-// solver the local solve is the same fixed linear operator for every column: its chain of launches with SpMM in place of
-// SpMV.  The block V-cycle reads the FP64 level matrices; under -dls1_amg_precision single the single-vector path reads
+// Slabs of w columns, row-major, through the composition above at width w (the `slab` instance): the restriction, the
+// prolongation and the operator at the width the assembly of E uses them at, the V-cycle on blocks that LOBPCG uses, and
+// the kernels of block_dev.h.  With the Chebyshev local solver the local solve is the same fixed linear operator for every
+// column: its chain of launches with SpMM in place of SpMV.  The block V-cycle reads the FP64 level matrices; under -dls1_amg_precision single the single-vector path reads
 // their float companions, so the two are then slightly different (fixed, linear, symmetric) operators.
 void PC::block_release() {
-  if (blk_graph) bk::graph_destroy(blk_graph);
-  blk_graph = nullptr;
-  blk_graph_fused = -1;
-  blk_graph_failed = false;
+  blk_chain.reset();
+  slab = App{};
   void* ptrs[] = {blk_r0, blk_r1, blk_z, blk_d, blk_x, blk_in, blk_out, blk_t1, blk_t2, blk_t3, blk_xe, blk_yE, blk_G,
                   blk_C, blk_ZR, blk_col, blk_dots, blk_dotwork, blk_coef, blk_g2e, blk_e2c};
   for (void* p : ptrs) bk::dfree(p);
@@ -1973,7 +1947,7 @@ void PC::block_release() {
   blk_g2e = blk_e2c = nullptr;
   blk_work.release();
   blk_w = blk_kp = 0;
-  blk_slabs = blk_columns = blk_padded = blk_graph_launches = blk_solves = 0;
+  blk_slabs = blk_columns = blk_padded = 0;
 }
 
 // Work space of the block entry points, allocated once per set-up (released by the next set-up and by destroy).
@@ -2017,6 +1991,13 @@ int PC::setup_block() {
     bk::h2d(blk_e2c, e2c.data(), sizeof(int) * e2c.size());
   }
   blk_w = w;
+  slab.w = w;
+  slab.coarse = blk_ZR != nullptr;
+  slab.wl = blk_r0; slab.xl = blk_x; slab.r1 = blk_r1; slab.z = blk_z; slab.d = blk_d;
+  slab.t1 = blk_t1; slab.t2 = blk_t2; slab.t3 = blk_t3;
+  slab.xe = slab.ye = blk_xe;
+  slab.work = &blk_work;
+  slab.chain = &blk_chain;
   return 0;
 }
 
@@ -2025,160 +2006,7 @@ void PC::block_info(int* width, long long* slabs, long long* columns, long long*
   if (slabs) *slabs = blk_slabs;
   if (columns) *columns = blk_columns;
   if (padded) *padded = blk_padded;
-  if (graph_launches) *graph_launches = blk_graph_launches;
-}
-
-// The K steps on the slab blk_r0 (the graph names its buffers, so the slab is fixed): WL holds the right-hand sides on entry and the solutions (dscale .* them) on return.  The
-// residual travels between WL and blk_r1 (out of place through the fused residual epilogue of the SpMM).
-void PC::block_steps(const double* dscale) {
-  double* const WL = blk_r0;
-  const int ns = (int)subs.size(), K = cheb_K, w = blk_w;
-  const bool fused = g_block_fused.load() != 0;
-  double *rc = WL, *ro = blk_r1;
-  for (int k = 0; k < K; ++k) {
-    amg1->vcycle(rc, w, blk_z, w, w);
-    const int flags = (k == 0 ? 1 : 0) | (k == K - 1 ? 2 : 0);
-    const double* ck = d_cheb_coef + (size_t)k * ns * 2;
-    if (fused) bk::cheb_dir_block(ch, ck, flags, blk_z, blk_d, blk_x, dscale, WL, w);
-    else cheb_dir_block_composed(ch, ck, flags, blk_z, blk_d, blk_x, dscale, WL, w, blk_work);
-    if (k == K - 1) break;
-    bk::spmm_fused(dirL, bk::EPI_RES, blk_d, w, ro, w, w, rc, w, nullptr, 0, nullptr, 0.0);   // r_out = r_in - A d
-    std::swap(rc, ro);
-  }
-}
-
-// [D] M^-1 [D] on a slab: local_solve_cheb with block kernels.  One linear chain on one stream, captured once per set-up
-// into a HIP graph of its own: the first slab goes out directly (the graph is recorded next to it), later ones replay, one
-// in eight goes direct while the in-situ kernel timer runs.
-void PC::local_solve_block() {
-  double* const WL = blk_r0;
-  if (nL == 0 || subs.empty()) return;
-  if (!d_cheb_coef || cheb_K <= 0 || !amg1) throw std::runtime_error("GenEO - solve KO: dls1 (-dls1_ksp_type chebyshev was not set up)");
-  const int w = blk_w;
-  if (opt.lvl1RAS) bk::block_rowscale(WL, w, WL, w, d_D, 1.0, 0.0, nL, w);
-  const double* dscale = opt.lvl1SRAS ? d_D : nullptr;
-  const int fused = g_block_fused.load();
-  if (!fused && !blk_work.t) blk_work.alloc(nL, (int)subs.size(), w);     // (before any capture: nothing is allocated inside one)
-  if (blk_graph && blk_graph_fused != fused) {
-    bk::graph_destroy(blk_graph);
-    blk_graph = nullptr;
-  }
-  bool direct = false;
-  if (!blk_graph) {
-    direct = true;
-    if (!blk_graph_failed && bk::graph_capture_begin()) {
-      try {
-        block_steps(dscale);
-      } catch (...) {
-        bk::graph_capture_end();
-        blk_graph_failed = true;
-        throw;
-      }
-      blk_graph = bk::graph_capture_end();
-      blk_graph_fused = fused;
-      if (!blk_graph) blk_graph_failed = true;
-    } else {
-      blk_graph_failed = true;
-    }
-  } else if (bk::spmv_profiling() && (blk_solves % 8 == 0)) {
-    direct = true;
-  }
-  ++blk_solves;
-  if (direct) {
-    block_steps(dscale);
-  } else {
-    bk::graph_launch(blk_graph);
-    ++blk_graph_launches;
-  }
-  info.dls1_iterations += cheb_K;     // one chain of K steps, whatever the width
-  info.dls1_solves += 1;
-}
-
-// YE <- E^-1 YE on the dimE x w block.  A host-made Cholesky factor on the device (dimE <= 1024): one launch for all
-// columns.  A factor made on the device, or one the host alone holds: column by column through the single-vector path.
-void PC::coarse_einv_block(double* YE) {
-  const int w = blk_w;
-  if (!E_dev && E_chol && d_EL && dimE <= 1024) {
-    const bool ok = g_block_fused.load() ? bk::chol_solve_block(d_EL, d_ELT, dimE, YE, w)
-                                         : chol_solve_block_composed_once(d_EL, d_ELT, dimE, YE, w);
-    if (ok) return;
-  }
-  for (int j = 0; j < w; ++j) {
-    bk::block_axpby(blk_col, 1, 1.0, YE + j, w, 0.0, dimE, 1);
-    coarse_einv(blk_col);
-    bk::block_axpby(YE + j, w, 1.0, blk_col, 1, 0.0, dimE, 1);
-  }
-}
-
-// blk_C[s] (kp x w) = the rows of E^-1 Z^T X that belong to subdomain s, Z^T X taken from the restricted slab XL
-void PC::coarse_solve_block(const double* XL) {
-  const int w = blk_w, kp = blk_kp, ns = (int)subs.size();
-  auto t0 = clk::now();
-  bk::gram(ch, blk_ZR, kp, kp, XL, w, w, blk_G);
-  bk::gather_rows(blk_yE, blk_G, blk_g2e, dimE, w);
-  allreduce(blk_yE, slab_entries(dimE, w));
-  auto t1 = clk::now();
-  coarse_einv_block(blk_yE);
-  bk::gather_rows(blk_C, blk_yE, blk_e2c, ns * kp, w);
-  info.lvl2ApplyZtTimeLoc += secs(t0, t1);
-  info.lvl2ApplyEinvTimeLoc += secs(t1, clk::now());
-}
-
-void PC::apply_q_block(const double* X, double* Y) {
-  const int w = blk_w;
-  if (!blk_ZR) {       // an empty coarse space: Q = 0
-    bk::zero(Y, sizeof(double) * (size_t)n_owned() * w);
-    return;
-  }
-  restrict_block(X, blk_x, w, blk_xe);
-  coarse_solve_block(blk_x);
-  bk::block_mul(ch, blk_ZR, blk_kp, blk_kp, blk_C, w, blk_r0, w, false);
-  prolong_block(blk_r0, Y, w, blk_xe);
-}
-
-// PC::apply on an owned slab, branch for branch
-void PC::apply_block(const double* X, double* Y) {
-  const int w = blk_w, nw = slab_entries(n_owned(), w);
-  auto t0 = clk::now();
-  if (opt.lvl2 && !opt.hybrid) {
-    restrict_block(X, blk_r0, w, blk_xe);
-    if (blk_ZR) coarse_solve_block(blk_r0);
-    auto t1 = clk::now();
-    local_solve_block();
-    auto t2 = clk::now();
-    if (blk_ZR) bk::block_mul(ch, blk_ZR, blk_kp, blk_kp, blk_C, w, blk_r0, w, true);
-    prolong_block(blk_r0, Y, w, blk_xe);
-    info.lvl2ApplyTimeLoc += secs(t0, t1);
-    info.lvl1ApplyMinvTimeLoc += secs(t1, t2);
-    info.lvl1ApplyTimeLoc += secs(t1, clk::now());
-    return;
-  }
-  bool have_q = false;
-  if (opt.lvl2 && !opt.effHybrid) {
-    apply_q_block(X, Y);
-    have_q = true;
-    info.lvl2ApplyTimeLoc += secs(t0, clk::now());
-  }
-  auto t1 = clk::now();
-  double* W = blk_t1;
-  bk::copy(W, X, nw);
-  if (opt.hybrid && !opt.effHybrid) {  // (I - P^T)
-    matmult_block(Y, blk_t2, w, blk_r0, blk_xe);
-    bk::axpy(W, -1.0, blk_t2, nw);
-  }
-  restrict_block(W, blk_r0, w, blk_xe);
-  auto t2 = clk::now();
-  local_solve_block();
-  info.lvl1ApplyMinvTimeLoc += secs(t2, clk::now());
-  prolong_block(blk_r0, W, w, blk_xe);
-  if (opt.hybrid) {  // (I - P)
-    matmult_block(W, blk_t2, w, blk_r0, blk_xe);
-    apply_q_block(blk_t2, blk_t3);
-    bk::axpy(W, -1.0, blk_t3, nw);
-  }
-  if (have_q) bk::axpy(Y, 1.0, W, nw);
-  else bk::copy(Y, W, nw);
-  info.lvl1ApplyTimeLoc += secs(t1, clk::now());
+  if (graph_launches) *graph_launches = blk_chain.replays;
 }
 
 int PC::block_check(const char* who, int ld, int m, const void* a, const void* b) {
@@ -2200,15 +2028,18 @@ void PC::slab_out(const double* slab, int m, double* Ycm, int ld) {
   else block_export_composed(slab, blk_w, n_owned(), m, Ycm, ld);
 }
 
-int PC::apply_mat(const double* X, int ldx, double* Y, int ldy, int m) {
-  if (int rc = block_check("PCMatApply_GenEO", std::min(ldx, ldy), m, X, Y)) return rc;
+// apply_mat (counted: blk_slabs / blk_columns / blk_padded) and matmult_mat, slab by slab
+int PC::slab_loop(bool apply, const double* X, int ldx, double* Y, int ldy, int m) {
+  if (int rc = block_check(apply ? "PCMatApply_GenEO" : "MatMatMult_GenEO", std::min(ldx, ldy), m, X, Y)) return rc;
   try {
     const int w = blk_w;
     for (int j0 = 0; j0 < m; j0 += w) {
       const int ms = std::min(w, m - j0);
       slab_in(X + (size_t)j0 * ldx, ldx, ms, blk_in);
-      apply_block(blk_in, blk_out);
+      if (apply) apply_on(slab, blk_in, blk_out);
+      else matmult(blk_in, blk_out, w, slab.wl, slab.xe, slab.ye);
       slab_out(blk_out, ms, Y + (size_t)j0 * ldy, ldy);
+      if (!apply) continue;
       blk_slabs += 1;
       blk_columns += ms;
       blk_padded += w - ms;
@@ -2218,22 +2049,8 @@ int PC::apply_mat(const double* X, int ldx, double* Y, int ldy, int m) {
   }
   return 0;
 }
-
-int PC::matmult_mat(const double* X, int ldx, double* Y, int ldy, int m) {
-  if (int rc = block_check("MatMatMult_GenEO", std::min(ldx, ldy), m, X, Y)) return rc;
-  try {
-    const int w = blk_w;
-    for (int j0 = 0; j0 < m; j0 += w) {
-      const int ms = std::min(w, m - j0);
-      slab_in(X + (size_t)j0 * ldx, ldx, ms, blk_in);
-      matmult_block(blk_in, blk_out, w, blk_r0, blk_xe);
-      slab_out(blk_out, ms, Y + (size_t)j0 * ldy, ldy);
-    }
-  } catch (std::exception& e) {
-    return fail(e.what());
-  }
-  return 0;
-}
+int PC::apply_mat(const double* X, int ldx, double* Y, int ldy, int m) { return slab_loop(true, X, ldx, Y, ldy, m); }
+int PC::matmult_mat(const double* X, int ldx, double* Y, int ldy, int m) { return slab_loop(false, X, ldx, Y, ldy, m); }
 
 // ------------------------------------------------------------------------------------ level 2
 // the local eigensolves of level 2 (buildCoarseSpaceWithGenEO, geneo.cpp:1243-1366): eigenvalues, kept counts, Z
@@ -3022,18 +2839,9 @@ int PC::lobpcg_solve(const EigProblem& P, int m, std::vector<double>& lam, doubl
     const bool direct = no_graph || !reduced || (fused_update && !have_R) || (bk::spmv_profiling() && (it % 8 == 1 || it == 4));
     if (!direct && !it_graph[par] && !it_graph_failed) {
       const int spmm_before = info.eig_spmm;
-      if (bk::graph_capture_begin()) {
-        try {
-          device_phase(!pipe);
-        } catch (...) {
-          bk::graph_capture_end();
-          throw;
-        }
-        it_graph[par] = bk::graph_capture_end();
-        graph_has_gram[par] = !pipe;
-      }
+      it_graph[par] = capture_graph(it_graph_failed, [&] { device_phase(!pipe); });
+      graph_has_gram[par] = !pipe;
       info.eig_spmm = spmm_before;   // recorded, not run
-      if (!it_graph[par]) it_graph_failed = true;
     }
     if (!direct && it_graph[par] && graph_has_gram[par] == !pipe) {
       bk::graph_launch(it_graph[par]);
@@ -4006,8 +3814,8 @@ int PC::check_global_rank() {
     bk::h2d(d_yE, unit.data(), sizeof(double) * dimE);
     unit[j] = 0.0;
     bk::z_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, d_yE, d_wL, false);
-    prolong_add(d_wL, d_t1);
-    restrict_to_local(d_t1, d_xL);
+    prolong(d_wL, d_t1, 1, d_ye);
+    restrict(d_t1, d_xL, 1, d_xe);
     bk::zt_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, kmax, d_xL, d_yE, dimE);
     allreduce(d_yE, dimE);
     bk::d2h(colv.data(), d_yE, sizeof(double) * dimE);
@@ -4108,9 +3916,9 @@ int PC::build_E() {
         }
       bk::h2d(dC, hC.data(), sizeof(double) * hC.size());
       bk::block_mul(ch, ZR, kp, kp, dC, W, WLb, W, false);
-      prolong_block(WLb, T1, W, xe);
-      matmult_block(T1, T2, W, WLb, xe);
-      restrict_block(T2, XLb, W, xe);
+      prolong(WLb, T1, W, xe);
+      matmult(T1, T2, W, WLb, xe, xe);
+      restrict(T2, XLb, W, xe);
       bk::gram(ch, ZR, kp, kp, XLb, W, W, dG);
       bk::d2h(hG.data(), dG, sizeof(double) * hG.size());
       for (int s = 0; s < ns; ++s)
@@ -4134,9 +3942,9 @@ int PC::build_E() {
     bk::h2d(d_yE, unit.data(), sizeof(double) * dimE);
     unit[j] = 0.0;
     bk::z_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, d_yE, d_wL, false);
-    prolong_add(d_wL, d_t1);
-    if (int rc = matmult(d_t1, d_t2)) return rc;
-    restrict_to_local(d_t2, d_xL);
+    prolong(d_wL, d_t1, 1, d_ye);
+    matmult(d_t1, d_t2, 1, d_wL, d_xe, d_ye);
+    restrict(d_t2, d_xL, 1, d_xe);
     bk::zt_apply(ch, d_Z, d_zbase, d_ksub, d_zoff, kmax, d_xL, d_yE, dimE);
     allreduce(d_yE, dimE);
     bk::d2h(colv.data(), d_yE, sizeof(double) * dimE);
@@ -4163,7 +3971,7 @@ int PC::build_E() {
     for (int a = 0; a < dimE; ++a)
       for (int b = 0; b <= a; ++b) EfacT[(size_t)b * dimE + a] = Efac[(size_t)a * dimE + b];
   }
-  if (E_chol && dimE > 0 && dimE <= 1024 && !want_dev) {     // the factor, twice, for the device sweeps of coarse_solve_local
+  if (E_chol && dimE > 0 && dimE <= 1024 && !want_dev) {     // the factor, twice, for the device sweeps of coarse_einv
     d_EL = (double*)bk::alloc(sizeof(double) * Efac.size());
     d_ELT = (double*)bk::alloc(sizeof(double) * EfacT.size());
     bk::h2d(d_EL, Efac.data(), sizeof(double) * Efac.size());
@@ -4262,50 +4070,49 @@ int PC::solve_cg(const double* b, double* x, KspResult* res) {
   DeviceVectors bufs;
   auto dv = [&](void) { return bufs.get(n); };
   double *r = dv(), *z = dv(), *p = dv(), *w = dv();
-  auto done = [&](int rc) { return rc; };
   ConvTest conv{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol};
   residual_history.clear();
   if (opt.ksp_guess_nonzero) {
-    if (int rc = matmult(x, r)) return done(rc);
+    if (int rc = matmult(x, r)) return rc;
     bk::axpby(r, 1.0, b, -1.0, n);  // r = b - A x
   } else {
     bk::copy(r, b, n);
   }
-  if (int rc = apply(r, z)) return done(rc);
+  if (int rc = apply(r, z)) return rc;
   double dp = std::sqrt(gdot(z, z));
   double snorm = -1.0;
   if (opt.ksp_guess_nonzero) {
-    if (int rc = apply(b, w)) return done(rc);
+    if (int rc = apply(b, w)) return rc;
     snorm = std::sqrt(gdot(w, w));
   }
   residual_history.push_back(dp);
   res->its = 0;
   res->rnorm = dp;
   res->reason = conv(0, dp, snorm);
-  if (res->reason) return done(0);
+  if (res->reason) return 0;
   double betaold = 0.0;
   for (int i = 0; i < opt.ksp_max_it; ++i) {
     res->its = i + 1;
     const double beta = gdot(z, r);
-    if (beta == 0.0) { res->reason = 3; return done(0); }
+    if (beta == 0.0) { res->reason = 3; return 0; }
     if (i == 0) bk::copy(p, z, n);
     else bk::axpby(p, 1.0, z, beta / betaold, n);  // p = z + b p
-    if (int rc = matmult(p, w)) return done(rc);
+    if (int rc = matmult(p, w)) return rc;
     const double dpi = gdot(p, w);
     betaold = beta;
-    if (!(dpi > 0.0)) { res->reason = -8; return done(0); }  // KSP_DIVERGED_INDEFINITE_MAT
+    if (!(dpi > 0.0)) { res->reason = -8; return 0; }  // KSP_DIVERGED_INDEFINITE_MAT
     const double a = beta / dpi;
     bk::axpy(x, a, p, n);
     bk::axpy(r, -a, w, n);
-    if (int rc = apply(r, z)) return done(rc);
+    if (int rc = apply(r, z)) return rc;
     dp = std::sqrt(gdot(z, z));
     residual_history.push_back(dp);
     res->rnorm = dp;
     res->reason = conv(i + 1, dp, -1.0);
-    if (res->reason) return done(0);
+    if (res->reason) return 0;
   }
   res->reason = -3;
-  return done(0);
+  return 0;
 }
 
 // h_out[j] = sum over ALL ranks of X[:, j] . Y[:, j] on owned slabs: one kernel pair, one all-reduce of w, one download
@@ -4352,7 +4159,7 @@ int PC::solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int*
     int* rs = reason + j0;
     slab_in(B + (size_t)j0 * ldb, ldb, ms, r);      // x = 0: r = b
     bk::zero(x, sizeof(double) * (size_t)nw);
-    apply_block(r, z);
+    apply_on(slab, r, z);
     applied(ms);
     slab_coldot(z, z, zz.data());
     int active = 0;
@@ -4382,7 +4189,7 @@ int PC::solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int*
       if (active == 0) break;
       if (i == 0) bk::copy(p, z, nw);
       else slab_cols(true, p, z, cb.data());        // p = z + b p
-      matmult_block(p, q, w, blk_r0, blk_xe);
+      matmult(p, q, w, slab.wl, slab.xe, slab.ye);
       slab_coldot(p, q, dpi.data());
       for (int j = 0; j < w; ++j) {
         ca[j] = 0.0;
@@ -4400,7 +4207,7 @@ int PC::solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int*
       slab_cols(false, x, p, ca.data());
       for (int j = 0; j < w; ++j) ca[j] = -ca[j];
       slab_cols(false, r, q, ca.data());
-      apply_block(r, z);
+      apply_on(slab, r, z);
       applied(ms);
       slab_coldot(z, z, zz.data());
       for (int j = 0; j < ms; ++j) {
@@ -4449,7 +4256,6 @@ int PC::solve_gmres(const double* b, double* x, KspResult* res) {
   DeviceVectors bufs;
   auto dvec = [&]() { return bufs.get(n); };
   double *t = dvec(), *w = dvec();
-  auto done = [&](int rc) { return rc; };
   ConvTest conv{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol};
   residual_history.clear();
   res->its = 0;
@@ -4459,26 +4265,26 @@ int PC::solve_gmres(const double* b, double* x, KspResult* res) {
     if (V.empty()) V.push_back(dvec());
     // r = M^-1 (b - A x)
     if (opt.ksp_guess_nonzero || !first) {
-      if (int rc = matmult(x, t)) return done(rc);
+      if (int rc = matmult(x, t)) return rc;
       bk::axpby(t, 1.0, b, -1.0, n);
-      if (int rc = apply(t, V[0])) return done(rc);
+      if (int rc = apply(t, V[0])) return rc;
     } else {
-      if (int rc = apply(b, V[0])) return done(rc);
+      if (int rc = apply(b, V[0])) return rc;
     }
     double rn = std::sqrt(gdot(V[0], V[0]));
     if (first) {
       double snorm = -1.0;
       if (opt.ksp_guess_nonzero) {
-        if (int rc = apply(b, w)) return done(rc);
+        if (int rc = apply(b, w)) return rc;
         snorm = std::sqrt(gdot(w, w));
       }
       residual_history.push_back(rn);
       res->rnorm = rn;
       res->reason = conv(0, rn, snorm);
-      if (res->reason) return done(0);
+      if (res->reason) return 0;
       first = false;
     }
-    if (rn == 0.0) { res->reason = 3; return done(0); }
+    if (rn == 0.0) { res->reason = 3; return 0; }
     bk::axpby(V[0], 1.0 / rn, V[0], 0.0, n);
     std::fill(g.begin(), g.end(), 0.0);
     g[0] = rn;
@@ -4486,8 +4292,8 @@ int PC::solve_gmres(const double* b, double* x, KspResult* res) {
     int reason = 0;
     while (k < m && res->its < opt.ksp_max_it) {
       if ((int)V.size() < k + 2) V.push_back(dvec());
-      if (int rc = matmult(V[k], t)) return done(rc);
-      if (int rc = apply(t, w)) return done(rc);
+      if (int rc = matmult(V[k], t)) return rc;
+      if (int rc = apply(t, w)) return rc;
       for (int j = 0; j <= k; ++j) h[(size_t)j * m + k] = gdot(V[j], w);  // classical GS: all dots first
       for (int j = 0; j <= k; ++j) bk::axpy(w, -h[(size_t)j * m + k], V[j], n);
       const double hn = std::sqrt(gdot(w, w));
@@ -4519,8 +4325,8 @@ int PC::solve_gmres(const double* b, double* x, KspResult* res) {
       yk[i] = s / h[(size_t)i * m + i];
     }
     for (int j = 0; j < k; ++j) bk::axpy(x, yk[j], V[j], n);
-    if (reason) { res->reason = reason; return done(0); }
-    if (res->its >= opt.ksp_max_it) { res->reason = -3; return done(0); }
+    if (reason) { res->reason = reason; return 0; }
+    if (res->its >= opt.ksp_max_it) { res->reason = -3; return 0; }
   }
 }
 

@@ -113,39 +113,27 @@ struct Options {
 // returns "" on success, otherwise the error message (same texts as the reference)
 std::string parse_option(Options& o, const std::string& key, const std::string& value);
 std::string validate_options(const Options& o);
-// validation switch "cheb_fused": 1 (default) bk::cheb_dir and bk::cheb_residual, 0 the same step and residual update
-// composed of backend.h primitives (block_colscale, axpy, xmy, copy; spmv, axpy)
+// validation switches: "cheb_fused" 1 (default) bk::cheb_dir and bk::cheb_residual, 0 the same step and residual update
+// composed of backend.h primitives (gather, block_colscale, axpy, block_rowscale, copy; spmv, axpy); "block_fused" 1
+// (default) the kernels of block_dev.h, 0 the same operations composed of backend.h primitives (the definitions the host
+// twin links)
 void set_cheb_fused(int on);
 int cheb_fused();
-struct ChebWork {   // scratch of the composed step: one vector, the de-interleaved coefficients, their gather indices
-  double *t = nullptr, *ab = nullptr;
-  int* idx = nullptr;
-  int n = 0, ns = 0;
-  void alloc(int n, int ns);
-  void release();
-};
-// core.cpp: bk::cheb_dir's arithmetic from backend.h primitives, on the caller's scratch / on scratch of its own
-bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
-                       const double* dscale, double* out, const ChebWork& w);
-bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* z, double* d, double* x,
-                            const double* dscale, double* out);
-
-// validation switch "block_fused": 1 (default) the kernels of block_dev.h, 0 the same operations composed of backend.h
-// primitives (the definitions the host twin links)
 void set_block_fused(int on);
 int block_fused();
-struct BlockWork {   // scratch of the composed block step: one slab, the coefficients spread over the columns, their gather indices
+struct StepWork {   // scratch of the composed step at width w: one slab, the coefficients spread over the columns, their gather indices
   double *t = nullptr, *ab = nullptr;
   int* idx = nullptr;
   int n = 0, ns = 0, w = 0;
   void alloc(int n, int ns, int w);
   void release();
 };
-// core.cpp: the operations of block_dev.h from backend.h primitives; the _once forms allocate their scratch, run, wait, free
-bool cheb_dir_block_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
-                             const double* dscale, double* Out, int w, const BlockWork& wk);
-bool cheb_dir_block_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
-                                  const double* dscale, double* Out, int w);
+// core.cpp: the arithmetic of bk::cheb_dir (w = 1) / bk::cheb_dir_block from backend.h primitives, on the caller's scratch;
+// the _once forms allocate their scratch, run, wait, free
+bool cheb_dir_composed(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                       const double* dscale, double* Out, int w, const StepWork& wk);
+bool cheb_dir_composed_once(const bk::Chunks& c, const double* coef_k, int flags, const double* Z, double* D, double* X,
+                            const double* dscale, double* Out, int w);
 bool block_import_composed(const double* Xcm, int ld, int n, int m, double* Yrm, int w);
 bool block_export_composed(const double* Xrm, int w, int n, int m, double* Ycm, int ld);
 bool block_coldot_composed_once(const double* X, const double* Y, int n, int w, double* out);
@@ -235,8 +223,8 @@ class PC {
   int n_owned() const { return (int)owned.size(); }
   int cheb_steps_per_solve() const { return cheb_K; }
   void cheb_counters(long long* solves, long long* graph_launches, long long* fused_residuals) const {
-    *solves = cheb_solves;
-    *graph_launches = cheb_graph_launches;
+    *solves = cheb_chain.runs;
+    *graph_launches = cheb_chain.replays;
     *fused_residuals = cheb_res_fused;
   }
   std::vector<double> cheb_table() const;   // the device coefficient table, K x nsub x 2 (download)
@@ -299,54 +287,66 @@ class PC {
   int cg_long_len = 0;         // length of the first chunk of a local solve once the first solve of this set-up is known (0: not yet, -1: never)
   bool cg_graph_failed = false;
   long long cg_chunks = 0;     // chunks issued so far (sampling of direct launches while the in-situ timer runs)
+  // A chain of launches captured once into a HIP graph and replayed (the Chebyshev local solve, one per width)
+  struct Replay {
+    void* graph = nullptr;
+    bool failed = false;
+    const void* buf = nullptr;          // what the graph was captured for: the buffer it names and the *_fused value
+    int fused = -1;                     // (recaptured when either changes)
+    long long runs = 0, replays = 0;    // runs so far, and those that replayed the graph (the others: direct launches)
+    int value = 0;                      // what the chain returned when it was recorded
+    template <class Body>
+    int run(const void* buf, int fused, Body&& body);   // the value of this run's chain
+    void reset();
+  };
+  // What an application of the preconditioner works on.  Two instances, filled by the set-up: `vec` (w = 1, always) and
+  // `slab` (w = -geneo_block_width, row-major slabs; w = 0 without one).  The slab path is the vector path at another width:
+  // restrict / prolong / matmult / cheb_steps / apply_on / apply_q_on take the width from here, and only local_solve and
+  // the coarse_* leaves branch on w == 1.
+  struct App {
+    int w = 0;
+    bool coarse = false;                 // Q is applied (slab: a non-empty coarse space; vec: its kernels take dimE = 0)
+    double *wl = nullptr, *xl = nullptr; // local: right-hand side -> result of the local solve; R x of apply_q = the chain's solution
+    double *r1 = nullptr, *z = nullptr, *d = nullptr;   // local, the chain's: second residual (ping-pong), V r, direction
+    double *t1 = nullptr, *t2 = nullptr, *t3 = nullptr; // owned temporaries of the generic composition
+    double *xe = nullptr, *ye = nullptr; // ext staging of the restriction / the prolongation
+    StepWork* work = nullptr;            // scratch of the composed step
+    Replay* chain = nullptr;
+  };
+  App vec, slab;
   // Chebyshev local solver: coefficient table coef[(k ns + s) 2 + {0, 1}] = (a_k, b_k) of subdomain s (rows k >= k_s are
-  // zero), K = max_s k_s steps per solve, the direction vector, and the HIP graph of one whole solve
+  // zero), K = max_s k_s steps per solve, and per width the HIP graph of one whole solve with its counters
+  // (PCGenEOGetLocalSolverCounters, PCGenEOGetBlockInfo) and the scratch of the composed step (vector: sized by setup_cheb;
+  // slab: by the first composed solve).  cheb_res_fused: residual updates r - A d of vector solves that went through
+  // bk::cheb_residual (the others: bk::spmv and bk::axpy).
   double* d_cheb_coef = nullptr;
   int cheb_K = 0;
-  void* cheb_graph = nullptr;
-  double* cheb_graph_wL = nullptr;   // the graph names its buffers and the step kernel's form: recaptured when either changes
-  int cheb_graph_fused = -1;
-  bool cheb_graph_failed = false;
-  long long cheb_solves = 0;
-  // what ran (PCGenEOGetLocalSolverCounters): solves replayed from the graph, and residual updates r - A d that went
-  // through bk::cheb_residual (the others: bk::spmv and bk::axpy); cheb_graph_res is the latter's count inside the graph
-  long long cheb_graph_launches = 0, cheb_res_fused = 0;
-  int cheb_graph_res = 0;
-  ChebWork cheb_work;   // scratch of the composed step, sized by setup_cheb
+  long long cheb_res_fused = 0;
+  Replay cheb_chain, blk_chain;
+  StepWork cheb_work, blk_work;
   int setup_cheb();
   void cheb_release();
-  int cheb_steps(double* wL, const double* dscale);   // returns the number of residual updates bk::cheb_residual took
-  void local_solve_cheb(double* wL);
+  int cheb_steps(const App& a, const double* dscale);   // returns the number of residual updates bk::cheb_residual took
   // Block entry points: slab width of this set-up (0: none), the work space (local slabs r -- two, ping-pong --, z, d, x;
   // owned slabs in / out / t1..t3; the ext staging slab; coarse right-hand sides, per-subdomain Gram rows and
-  // coefficients), the row-major Z, the index maps between Gram rows, coarse rows and coefficient rows, the HIP graph of
-  // one slab's local solve, and the counters of PCGenEOGetBlockInfo
+  // coefficients), the row-major Z, the index maps between Gram rows, coarse rows and coefficient rows, and the counters
+  // of PCGenEOGetBlockInfo
   int blk_w = 0, blk_kp = 0;
   double *blk_r0 = nullptr, *blk_r1 = nullptr, *blk_z = nullptr, *blk_d = nullptr, *blk_x = nullptr;
   double *blk_in = nullptr, *blk_out = nullptr, *blk_t1 = nullptr, *blk_t2 = nullptr, *blk_t3 = nullptr, *blk_xe = nullptr;
   double *blk_yE = nullptr, *blk_G = nullptr, *blk_C = nullptr, *blk_ZR = nullptr, *blk_col = nullptr;
   double *blk_dots = nullptr, *blk_dotwork = nullptr, *blk_coef = nullptr;
   int *blk_g2e = nullptr, *blk_e2c = nullptr;
-  void* blk_graph = nullptr;
-  int blk_graph_fused = -1;
-  bool blk_graph_failed = false;
-  long long blk_slabs = 0, blk_columns = 0, blk_padded = 0, blk_graph_launches = 0, blk_solves = 0;
-  BlockWork blk_work;
+  long long blk_slabs = 0, blk_columns = 0, blk_padded = 0;
   int setup_block();
   void block_release();
   int block_check(const char* who, int ld, int m, const void* a, const void* b);
-  void block_steps(const double* dscale);
-  void local_solve_block();                                        // on blk_r0
-  void coarse_einv_block(double* YE);
-  void coarse_solve_block(const double* XL);                       // blk_C = per-subdomain rows of E^-1 Z^T X (from XL)
-  void apply_q_block(const double* X, double* Y);
-  void apply_block(const double* X, double* Y);                    // owned slabs, mirrors apply() branch for branch
+  int slab_loop(bool apply, const double* X, int ldx, double* Y, int ldy, int m);   // apply_mat / matmult_mat
   void slab_in(const double* Xcm, int ld, int m, double* slab);
   void slab_out(const double* slab, int m, double* Ycm, int ld);
   void slab_coldot(const double* X, const double* Y, double* h_out);
   void slab_cols(bool xpby, double* A, const double* B, const double* h_c);
   int solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
-  void coarse_einv(double* yE);                                    // yE <- E^-1 yE (the factor's own path)
   HostCsr host_neu_cache, host_dir_cache;   // block-diagonal host copies of A_Neu / the level-1 matrix, reused by the next set-up
   AmgDevice* amg1 = nullptr;   // hierarchy of the level-1 (Dirichlet / Robin) block-diagonal matrix (local solves)
   AmgDevice* amgN = nullptr;   // hierarchy of the Neumann block-diagonal matrix (LOBPCG preconditioner)
@@ -398,13 +398,18 @@ class PC {
   int eigen_dense_host();
   int eigen_lobpcg();
   int build_E();
-  void restrict_to_local(const double* x_owned, double* xL);      // R  (applyLevel1Scatter)
-  void prolong_add(const double* wL, double* y_owned);            // sum R^T (applyLevel1Gather)
-  void restrict_block(const double* X, double* XL, int w, double* xe);
-  void prolong_block(const double* WL, double* Y, int w, double* ye);
-  void matmult_block(const double* X, double* Y, int w, double* WL, double* xe);
-  void local_solve(double* wL);                                   // [D] M^-1 [D]
-  void coarse_solve_local(const double* xL, double* yE);          // yE = E^-1 Z^T x (from xL)
+  // R (applyLevel1Scatter), sum R^T (applyLevel1Gather) and A = sum R^T A_Neu R on w vectors (w > 1: row-major); at
+  // w > 1 the halo buffers hold w x the single-vector counts and the exchange callback gets flag = reverse | w << 1
+  void restrict(const double* X, double* XL, int w, double* xe);
+  void prolong(const double* WL, double* Y, int w, double* ye);
+  void matmult(const double* X, double* Y, int w, double* WL, double* xe, double* ye);
+  void local_solve_cg(double* wL);                                // [D] M^-1 [D]: batched PCG (vector only)
+  void local_solve(const App& a);                                 // [D] M^-1 [D] on a.wl: PCG (w = 1) or the Chebyshev chain
+  void coarse_einv(double* yE, int w);                            // yE <- E^-1 yE (the factor's own path)
+  void coarse_solve(const App& a, const double* XL);              // coarse coefficients E^-1 Z^T x (from the restricted XL)
+  void coarse_expand(const App& a, double* WL, bool add);         // WL (+)= Z times those coefficients
+  void apply_q_on(const App& a, const double* X, double* Y);
+  void apply_on(const App& a, const double* X, double* Y);
   void allreduce(double* dev, int n);
   double gdot(const double* x, const double* y);
   int solve_cg(const double* b, double* x, KspResult* res);

@@ -1,6 +1,7 @@
 """Worker of tests/test_block_rhs_gloo.py: two ranks over gloo on the host twin, four of the eight subdomains each;
-PCMatApply_GenEO and KSPMatSolve_GenEO on the owned rows of a block given by the test, and the set-up error of halo
-buffers narrower than the block width."""
+PCMatApply_GenEO and KSPMatSolve_GenEO on the owned rows of a block given by the test, the set-up error of halo
+buffers narrower than the block width, and the flags the exchange callback receives from a single-vector apply and
+matmult and from a block apply."""
 import json
 import os
 import sys
@@ -30,8 +31,16 @@ def main():
     data = np.load(in_path)
     Xa, Bs = data["Xa"][plan.owned], data["Bs"][plan.owned]
 
+    class RecordingComm(TorchComm):
+        flags = None
+
+        def exchange(self, user, flag):
+            if self.flags is not None:
+                self.flags.add(int(flag))
+            return super().exchange(user, flag)
+
     def make(width):
-        comm = TorchComm(plan, "cpu")
+        comm = RecordingComm(plan, "cpu")
         pc = GenEOPC(lib)
         pc.set_from_options(argv + ["-geneo_block_width", str(w)])
         pc.set_sizes(n ** 3, nb)
@@ -51,13 +60,19 @@ def main():
     narrow.destroy()
     pc, comm = make(None)
     pc.setup(None)
+    comm.flags = set()
+    pc.apply(np.ascontiguousarray(Xa[:, 0]))
+    pc.matmult(np.ascontiguousarray(Xa[:, 0]))
+    flags_vector, comm.flags = sorted(comm.flags), set()
     Y = pc.mat_apply(Xa)
+    flags_block, comm.flags = sorted(comm.flags), None
     X, its, rnorm, reasons = pc.mat_solve(Bs)
     full = lambda A: np.stack([gather_owned(np.ascontiguousarray(A[:, j]), plan, n ** 3) for j in range(A.shape[1])], axis=1)
     Yf, Xf = full(Y), full(X)
     if rank == 0:
         np.savez(out_path, Y=Yf, X=Xf, meta=json.dumps(dict(its=[int(v) for v in its], reasons=list(reasons), narrow=err,
-                                                         info=pc.block_info())))
+                                                         info=pc.block_info(), flags_vector=flags_vector,
+                                                         flags_block=flags_block)))
     if comm.error is not None:
         raise comm.error
     dist.barrier()

@@ -1,12 +1,14 @@
 """Blocks of right-hand sides on two ranks (CPU, gloo, host twin): PCMatApply_GenEO and KSPMatSolve_GenEO at world size 2
 equal the one-rank results -- the apply to the parity bound of tests/block_rhs_util.py, the solve with the same counts and
-reasons per column -- and halo buffers narrower than the block width are a set-up error."""
+reasons per column --, halo buffers narrower than the block width are a set-up error, and the exchange callback gets the
+plain direction flag from the single-vector path and direction | width << 1 from the block path."""
 import json
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 import block_rhs_util as U
 import cases
@@ -17,9 +19,10 @@ W = 16
 ARGV = ["-geneo_lvl", "ASM,1"] + U.BASE + U.SOLVE
 
 
-def test_two_ranks_equal_one_rank(tmp_path):
-    from hostsim_util import hostsim_lib
-    lib = hostsim_lib()
+@pytest.fixture(scope="module")
+def two_ranks(tmp_path_factory):
+    """one two-rank run for the tests of this module: (inputs Xa, Bs; the worker's arrays; its meta record)"""
+    tmp_path = tmp_path_factory.mktemp("block_gloo")
     mesh, dec, a, b = cases.grid_case(12, 3, (2, 2, 2), 1)
     N = mesh.nbNode
     Xa = U.rhs_block(N, 17, 31)                                     # two slabs, the second padded
@@ -34,7 +37,22 @@ def test_two_ranks_equal_one_rank(tmp_path):
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     got = np.load(out)
-    meta = json.loads(str(got["meta"]))
+    return Xa, Bs, got, json.loads(str(got["meta"]))
+
+
+def test_exchange_flags(two_ranks):
+    """A host's callback written for single vectors may compare the flag with 0 and 1: no width bits at width 1."""
+    meta = two_ranks[3]
+    assert meta["flags_vector"] == [0, 1]
+    assert meta["flags_block"] == [0 | W << 1, 1 | W << 1]
+
+
+def test_two_ranks_equal_one_rank(two_ranks):
+    from hostsim_util import hostsim_lib
+    lib = hostsim_lib()
+    mesh, dec, a, b = cases.grid_case(12, 3, (2, 2, 2), 1)
+    N = mesh.nbNode
+    Xa, Bs, got, meta = two_ranks
     assert "-geneo_block_width" in meta["narrow"] and "PCGenEOSetCommWidth" in meta["narrow"], meta["narrow"]
     pc = cases.run_pc(lib, mesh, dec, ARGV + ["-geneo_block_width", str(W)], b)
     Y1 = pc.mat_apply(Xa)
