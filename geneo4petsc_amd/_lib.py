@@ -99,6 +99,7 @@ SYMBOLS = {
     "MatMatMult_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "KSPMatSolve_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_int_p, c_dbl_p, c_int_p]),
     "PCGenEOGetBlockInfo": (C.c_int, [C.c_void_p, c_int_p] + [C.POINTER(C.c_longlong)] * 4),
+    "PCGenEOGetCoarseBlockCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
     "PCGenEOGetInfo": (C.c_int, [C.c_void_p, C.POINTER(GeneoInfo)]),
     "PCGenEOGetEigenvalues": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
     "PCGenEOGetCandidates": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
@@ -174,6 +175,7 @@ SYMBOLS = {
     "PCGenEOGetLocalSolverCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
     "GeneoTestCoarseFactor": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
     "GeneoTestCoarseSolve": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int]),
+    "GeneoTestCoarseSolveBlock": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int]),
     "GeneoTestCoarseElapsed": (C.c_int, [c_dbl_p, c_dbl_p]),
     "GeneoTestCgSteps": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 6 + [c_dbl_p]),
     "GeneoTestCsrOp": (C.c_longlong, [C.c_int, C.POINTER(GeneoCsr), C.POINTER(GeneoCsr), c_int_p, c_dbl_p, C.POINTER(C.c_void_p),

@@ -396,6 +396,11 @@ int PCGenEOGetBlockInfo(PC pc, int* width, long long* slabs, long long* columns,
   pc->ctx->block_info(width, slabs, columns, padded, graph_launches);
   return 0;
 }
+int PCGenEOGetCoarseBlockCounters(PC pc, long long* blocked, long long* by_column, long long* host_blocks) {
+  if (!pc || !pc->ctx) return -1;
+  pc->ctx->coarse_block_counters(blocked, by_column, host_blocks);
+  return 0;
+}
 int PCGenEOGetResidualHistory(PC pc, double* hist, int cap) {
   if (!pc || !pc->ctx) return 0;
   const auto& h = pc->ctx->residual_history;
@@ -1171,6 +1176,43 @@ int GeneoTestCoarseSolve(int n, int nb, const double* L, const double* LT, doubl
     dLT.fetch("LT", LT);
     dy0.fetch("y (input copy)", y);
     std::copy_n(dy.fetch("y"), n, y);
+    return 0;
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    return -1;
+  }
+}
+
+// The blocked sweeps on the n x w row-major block Y (bk::coarse_solve_block); the device time of one repetition goes where
+// GeneoTestCoarseSolve puts its own.
+int GeneoTestCoarseSolveBlock(int n, int nb, int w, const double* L, const double* LT, double* Y, int reps) {
+  try {
+    if (n < 0 || w < 1 || !L || !LT || !Y || reps < 1) throw std::runtime_error("GeneoTestCoarseSolveBlock: bad arguments");
+    const size_t nn = (size_t)n * n, nw = (size_t)n * w;
+    PaddedBuf dy0(nw, Y), dy(nw, nullptr), dL(nn, L), dLT(nn, LT);
+    void* e0 = bk::event_create();
+    void* e1 = bk::event_create();
+    bool have = true;
+    std::string err;
+    bk::event_record(e0);
+    try {
+      for (int r = 0; r < reps && have; ++r) {   // every repetition solves the caller's Y again
+        bk::d2d(dy.ptr(), dy0.ptr(), sizeof(double) * nw);
+        have = bk::coarse_solve_block(dL.ptr(), dLT.ptr(), n, nb, dy.ptr(), w);
+      }
+    } catch (std::exception& e) {
+      err = e.what();
+    }
+    bk::event_record(e1);
+    if (have && err.empty()) g_coarse_solve_ms = (double)bk::event_elapsed_ms(e0, e1) / reps;
+    bk::event_destroy(e0);
+    bk::event_destroy(e1);
+    if (!err.empty()) throw std::runtime_error(err);
+    if (!have) return -3;
+    dL.fetch("L", L);
+    dLT.fetch("LT", LT);
+    dy0.fetch("Y (input copy)", Y);
+    std::copy_n(dy.fetch("Y"), nw, Y);
     return 0;
   } catch (std::exception& e) {
     g_global_err = e.what();

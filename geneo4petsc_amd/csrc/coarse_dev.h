@@ -15,4 +15,10 @@ bool coarse_factor(const double* E, int n, int nb, double* L, double* LT, int* s
 // one-workgroup substitution on nb unknowns.  Stream-ordered, no synchronisation, fixed summation orders.
 bool coarse_solve(const double* L, const double* LT, int n, int nb, double* y);
 
+// Y <- (L L^T)^-1 Y in place on the n x w row-major slab Y (w = 16 | 32, leading dimension w), any n: the two launches per
+// block row of coarse_solve, each for all w columns together (4 ceil(n / nb) - 2 launches per slab).  Every element is one
+// accumulation chain over its own column in a fixed order: a column's bits depend neither on its position, nor on its
+// neighbours, nor on w, and a zero column stays +0.  Stream-ordered, no synchronisation, no allocation, no atomics.
+bool coarse_solve_block(const double* L, const double* LT, int n, int nb, double* Y, int w);
+
 }  // namespace bk

@@ -21,6 +21,14 @@
 // Sweeps, y <- (L L^T)^-1 y: per block row k_coarse_diag_solve (the scheme of k_chol_solve on nb unknowns, one workgroup)
 // and k_coarse_gemv (the rows still to come minus their nb columns times the block just solved; one wave per row, lanes
 // stride the columns, xor-butterfly sum: all fixed orders).  Forward with L below the block, backward with L^T above it.
+//
+// Sweeps on a block, Y <- (L L^T)^-1 Y with Y the n x w row-major slab (w = 16 | 32): the same two launches per block row,
+// for all w columns together.  k_coarse_diag_solve_block is k_coarse_diag_solve with one workgroup per column (the same
+// operations in the same order on Y[(k0 + t) w + j]); k_coarse_update_block is the matrix product of the rows still to
+// come with the block just solved on v_mfma_f64_16x16x4_f64 -- one wave per 16-row tile, one or two 16-column tiles per
+// wave, M enters negated and the accumulator starts at Y, so that it holds Y - M Y in ascending k.  An element of the
+// result is one accumulation chain over its own column; the column's position, its neighbours and w do not enter.  Lanes
+// outside the block (a ragged last row tile, kb no multiple of 4) feed exact zeros and store nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -299,6 +307,135 @@ bool coarse_solve(const double* L, const double* LT, int n, int nb, double* y) {
     const int kb = std::min(nb, n - k0), th = ((kb + 63) / 64) * 64;
     hipLaunchKernelGGL((k_coarse_diag_solve<16>), dim3(1), dim3(th), 0, s, L, LT, n, k0, kb, y, 1);
     if (k0 > 0) hipLaunchKernelGGL(k_coarse_gemv, dim3((k0 + 3) / 4), dim3(256), 0, s, LT, n, k0, kb, 0, k0, y);
+  }
+  HIPCHK(hipGetLastError());
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------ sweeps on a block
+// k_coarse_diag_solve on column j = blockIdx.x of the n x w row-major slab Y
+template <int PB>
+__global__ __launch_bounds__(CF_MAXB) void k_coarse_diag_solve_block(const double* __restrict__ L,
+                                                                     const double* __restrict__ LT, int n, int k0, int kb,
+                                                                     double* __restrict__ Y, int w, int backward) {
+  __shared__ double xs[CF_MAXB];
+  const int t = threadIdx.x;
+  double* y = Y + (int64_t)k0 * w + blockIdx.x;
+  double yv = (t < kb) ? y[(int64_t)t * w] : 0.0;
+  const double dg = (t < kb) ? L[(int64_t)(k0 + t) * n + k0 + t] : 1.0;
+  if (!backward) {
+    for (int q0 = 0; q0 < kb; q0 += PB) {
+      double c[PB];
+#pragma unroll
+      for (int p = 0; p < PB; ++p) {
+        const int k = q0 + p;
+        c[p] = (k < kb && t > k && t < kb) ? LT[(int64_t)(k0 + k) * n + k0 + t] : 0.0;
+      }
+#pragma unroll
+      for (int p = 0; p < PB; ++p) {
+        const int k = q0 + p;
+        if (k < kb) {                                   // (uniform)
+          if (t == k) { yv = yv / dg; xs[k] = yv; }
+          __syncthreads();
+          if (t > k) yv -= c[p] * xs[k];
+        }
+      }
+    }
+  } else {
+    for (int q0 = 0; q0 < kb; q0 += PB) {
+      double c[PB];
+#pragma unroll
+      for (int p = 0; p < PB; ++p) {
+        const int k = kb - 1 - (q0 + p);
+        c[p] = (k >= 0 && t < k) ? L[(int64_t)(k0 + k) * n + k0 + t] : 0.0;
+      }
+#pragma unroll
+      for (int p = 0; p < PB; ++p) {
+        const int k = kb - 1 - (q0 + p);
+        if (k >= 0) {
+          if (t == k) { yv = yv / dg; xs[k] = yv; }
+          __syncthreads();
+          if (t < k) yv -= c[p] * xs[k];
+        }
+      }
+    }
+  }
+  if (t < kb) y[(int64_t)t * w] = yv;
+}
+
+// Y[r][:] -= sum_c M[r][k0 + c] Y[k0 + c][:], c < kb, for the rows r0 <= r < r1 (none of them in the block: the rows read
+// and the rows written are disjoint, so the update is in place).  One wave per 16-row tile, CT column tiles of 16 (w = 16 CT).
+template <int CT>
+__global__ __launch_bounds__(256) void k_coarse_update_block(const double* __restrict__ M, int n, int k0, int kb, int r0,
+                                                             int r1, double* Y) {
+  constexpr int w = 16 * CT;
+  const int l = threadIdx.x & 63, li = l & 15, lk = l >> 4;
+  const int rt = r0 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+  if (rt >= r1) return;                                 // (wave-uniform)
+  d4 acc[CT];
+#pragma unroll
+  for (int b = 0; b < CT; ++b)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int row = rt + lk + 4 * v;
+      acc[b][v] = (row < r1) ? Y[(int64_t)row * w + 16 * b + li] : 0.0;
+    }
+  // Operands: every lane loads from an address inside the block (row and k clamped) and lanes outside it take an exact
+  // zero instead of what they loaded: the loads carry no predicate, so those of several k steps are in flight together.
+  const bool aok = rt + li < r1;
+  const double* ap = M + (int64_t)(aok ? rt + li : r0) * n + k0;
+  const double* bp = Y + (int64_t)k0 * w + li;
+  for (int k8 = 0; k8 < kb; k8 += 32) {                 // eight k steps' loads at a time
+    double av[8], bv[8][CT];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = k8 + 4 * u + lk;
+      const bool kok = k < kb;
+      const int kc = kok ? k : kb - 1;
+      const double a = ap[kc];
+      av[u] = (aok && kok) ? -a : 0.0;
+#pragma unroll
+      for (int b = 0; b < CT; ++b) {
+        const double y = bp[(int64_t)kc * w + 16 * b];
+        bv[u][b] = kok ? y : 0.0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (k8 + 4 * u < kb) {                            // (uniform)
+#pragma unroll
+        for (int b = 0; b < CT; ++b) acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u][b], acc[b], 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int b = 0; b < CT; ++b)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int row = rt + lk + 4 * v;
+      if (row < r1) Y[(int64_t)row * w + 16 * b + li] = acc[b][v];
+    }
+}
+
+static void update_block(hipStream_t s, const double* M, int n, int k0, int kb, int r0, int r1, double* Y, int w) {
+  const int wg = ((r1 - r0 + 15) / 16 + 3) / 4;
+  if (w == 16) hipLaunchKernelGGL((k_coarse_update_block<1>), dim3(wg), dim3(256), 0, s, M, n, k0, kb, r0, r1, Y);
+  else hipLaunchKernelGGL((k_coarse_update_block<2>), dim3(wg), dim3(256), 0, s, M, n, k0, kb, r0, r1, Y);
+}
+
+bool coarse_solve_block(const double* L, const double* LT, int n, int nb, double* Y, int w) {
+  if (!block_ok(nb)) throw std::runtime_error("coarse_solve_block: the block size must be a multiple of 16 in 16 .. 256");
+  if (w != 16 && w != 32) throw std::runtime_error("coarse_solve_block: width is not 16 or 32");
+  if (n <= 0) return true;
+  hipStream_t s = (hipStream_t)get_stream();
+  for (int k0 = 0; k0 < n; k0 += nb) {                  // L Z = Y
+    const int kb = std::min(nb, n - k0), th = ((kb + 63) / 64) * 64;
+    hipLaunchKernelGGL((k_coarse_diag_solve_block<16>), dim3(w), dim3(th), 0, s, L, LT, n, k0, kb, Y, w, 0);
+    if (k0 + kb < n) update_block(s, L, n, k0, kb, k0 + kb, n, Y, w);
+  }
+  for (int k0 = ((n - 1) / nb) * nb; k0 >= 0; k0 -= nb) {   // L^T X = Z, from the last block up
+    const int kb = std::min(nb, n - k0), th = ((kb + 63) / 64) * 64;
+    hipLaunchKernelGGL((k_coarse_diag_solve_block<16>), dim3(w), dim3(th), 0, s, L, LT, n, k0, kb, Y, w, 1);
+    if (k0 > 0) update_block(s, LT, n, k0, kb, 0, k0, Y, w);
   }
   HIPCHK(hipGetLastError());
   return true;

@@ -45,6 +45,7 @@
 namespace bk {
 __attribute__((weak)) bool coarse_factor(const double*, int, int, double*, double*, int*) { return false; }
 __attribute__((weak)) bool coarse_solve(const double*, const double*, int, int, double*) { return false; }
+__attribute__((weak)) bool coarse_solve_block(const double*, const double*, int, int, double*, int) { return false; }
 }  // namespace bk
 
 // The step of the Chebyshev local solver composed of backend.h primitives, at any width (w = 1: the vector step of
@@ -1797,8 +1798,14 @@ void PC::local_solve(const App& a) {
 }
 
 // yE <- E^-1 yE on w coarse vectors (w > 1: the dimE x w row-major block) by the path of the factor this set-up made (see
-// coarse_solve).  A block with a host-made Cholesky factor on the device (dimE <= 1024): one launch for all columns;
-// otherwise column by column through the single-vector path.
+// coarse_solve).  A block, by the factor:
+//   * made on the device (any dimE): the blocked sweeps on the whole block, bk::coarse_solve_block -- the launches of one
+//     single-vector sweep pair for all w columns (counted: coarse_blk_blocked);
+//   * made on the host and uploaded (Cholesky, dimE <= 1024): bk::chol_solve_block, one launch for all columns;
+//   * held on the host (Cholesky or LU, nothing uploaded): one download of the block, the w host solves of the
+//     single-vector path on the same column values (hence its bits), one upload (coarse_blk_host).
+// Where a block kernel answers "not available", and under GeneoSetKernelVariant("block_fused", 0), a device factor goes
+// column by column through the single-vector path (coarse_blk_by_column): the fallback and the comparison.
 void PC::coarse_einv(double* yE, int w) {
   if (w > 1) {
     if (!E_dev && E_chol && d_EL && dimE <= 1024) {
@@ -1806,11 +1813,29 @@ void PC::coarse_einv(double* yE, int w) {
                                            : chol_solve_block_composed_once(d_EL, d_ELT, dimE, yE, w);
       if (ok) return;
     }
+    if (E_dev && g_block_fused.load() && bk::coarse_solve_block(d_EL, d_ELT, dimE, E_nb, yE, w)) {
+      coarse_blk_blocked += 1;
+      return;
+    }
+    if (!d_EL) {
+      h_yEblk.resize((size_t)dimE * w);
+      bk::d2h(h_yEblk.data(), yE, sizeof(double) * h_yEblk.size());
+      for (int j = 0; j < w; ++j) {
+        for (int i = 0; i < dimE; ++i) h_yE[i] = h_yEblk[(size_t)i * w + j];
+        if (E_chol) dense::cholesky_solve_lu(Efac, EfacT, dimE, h_yE.data());
+        else dense::lu_solve(Efac, dimE, Epiv, h_yE.data());
+        for (int i = 0; i < dimE; ++i) h_yEblk[(size_t)i * w + j] = h_yE[i];
+      }
+      bk::h2d(yE, h_yEblk.data(), sizeof(double) * h_yEblk.size());
+      coarse_blk_host += 1;
+      return;
+    }
     for (int j = 0; j < w; ++j) {
       bk::block_axpby(blk_col, 1, 1.0, yE + j, w, 0.0, dimE, 1);
       coarse_einv(blk_col, 1);
       bk::block_axpby(yE + j, w, 1.0, blk_col, 1, 0.0, dimE, 1);
     }
+    coarse_blk_by_column += 1;
   } else if (E_dev) {
     if (!bk::coarse_solve(d_EL, d_ELT, dimE, E_nb, yE)) throw std::runtime_error("GenEO - solve KO: dcs2 (no blocked coarse sweeps on this backend)");
   } else if (!(E_chol && d_EL && bk::chol_solve(d_EL, d_ELT, dimE, yE))) {
@@ -1948,6 +1973,7 @@ void PC::block_release() {
   blk_work.release();
   blk_w = blk_kp = 0;
   blk_slabs = blk_columns = blk_padded = 0;
+  coarse_blk_blocked = coarse_blk_by_column = coarse_blk_host = 0;
 }
 
 // Work space of the block entry points, allocated once per set-up (released by the next set-up and by destroy).
@@ -2007,6 +2033,12 @@ void PC::block_info(int* width, long long* slabs, long long* columns, long long*
   if (columns) *columns = blk_columns;
   if (padded) *padded = blk_padded;
   if (graph_launches) *graph_launches = blk_chain.replays;
+}
+
+void PC::coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const {
+  if (blocked) *blocked = coarse_blk_blocked;
+  if (by_column) *by_column = coarse_blk_by_column;
+  if (host_blocks) *host_blocks = coarse_blk_host;
 }
 
 int PC::block_check(const char* who, int ld, int m, const void* a, const void* b) {

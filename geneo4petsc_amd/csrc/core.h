@@ -220,6 +220,9 @@ class PC {
   // since the set-up: slabs applied by apply_mat (KSPMatSolve's included), their columns, the zero columns that padded
   // them, and the local solves of slabs replayed from the HIP graph (the others went out as direct launches)
   void block_info(int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) const;
+  // since the set-up: slab applications of E^-1 by the blocked block sweeps (bk::coarse_solve_block), column by column
+  // through the single-vector path, and by one host round trip of the whole block (PCGenEOGetCoarseBlockCounters)
+  void coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const;
   int n_owned() const { return (int)owned.size(); }
   int cheb_steps_per_solve() const { return cheb_K; }
   void cheb_counters(long long* solves, long long* graph_launches, long long* fused_residuals) const {
@@ -265,7 +268,7 @@ class PC {
   bool E_dev = false;     // d_EL / d_ELT were factored on the device (block size E_nb): blocked sweeps in coarse_solve_local
   int E_nb = 0;
   bool factor_E_on_device(const std::vector<double>& sym);
-  std::vector<double> h_yE;
+  std::vector<double> h_yE, h_yEblk;   // host staging of one coarse vector / of a dimE x w block (coarse_einv)
   std::vector<double> h_Dscratch;   // partition of unity on the host, reused by the next set-up
   double cheb_lmax = 2.0, cheb_lmax1 = 2.0;
   struct Amg1Pending;
@@ -338,6 +341,7 @@ class PC {
   double *blk_dots = nullptr, *blk_dotwork = nullptr, *blk_coef = nullptr;
   int *blk_g2e = nullptr, *blk_e2c = nullptr;
   long long blk_slabs = 0, blk_columns = 0, blk_padded = 0;
+  long long coarse_blk_blocked = 0, coarse_blk_by_column = 0, coarse_blk_host = 0;   // coarse_block_counters
   int setup_block();
   void block_release();
   int block_check(const char* who, int ld, int m, const void* a, const void* b);

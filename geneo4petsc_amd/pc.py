@@ -286,6 +286,14 @@ class GenEOPC:
             raise GenEOError("PCGenEOGetBlockInfo: bad handle")
         return dict(width=w.value, slabs=v[0].value, columns=v[1].value, padded=v[2].value, graph_launches=v[3].value)
 
+    def coarse_block_counters(self):
+        """PCGenEOGetCoarseBlockCounters since the set-up: slab applications of E^-1 by the blocked sweeps on the whole block,
+        column by column through the single-vector path, and by one host round trip of the block."""
+        v = [C.c_longlong(0) for _ in range(3)]
+        if self.lib.PCGenEOGetCoarseBlockCounters(self.h, *[C.byref(x) for x in v]) < 0:
+            raise GenEOError("PCGenEOGetCoarseBlockCounters: bad handle")
+        return dict(blocked=v[0].value, by_column=v[1].value, host_blocks=v[2].value)
+
     def residual_history(self):
         n = self.lib.PCGenEOGetResidualHistory(self.h, None, 0)
         out = np.zeros(max(1, n))

@@ -211,6 +211,13 @@ PetscErrorCode KSPMatSolve_GenEO(GENEO_PC pc, const double* B_dev, int ldb, doub
  * unavailable).  Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
 int PCGenEOGetBlockInfo(GENEO_PC pc, int* width, long long* slabs, long long* columns, long long* padded,
                         long long* graph_launches);
+/* Since the set-up: how the slabs of the block apply had E^-1 applied to their dimE x w coarse block -- *blocked by the
+ * blocked device sweeps on the whole block (a factor made on the device: the launches of one single-vector sweep pair for
+ * all w columns), *by_column column by column through the single-vector path (GeneoSetKernelVariant("block_fused", 0), or
+ * a backend without the block kernel), *host_blocks by one download, w host solves and one upload (a factor held on the
+ * host).  Slabs that took the one-launch kernel of a host-made factor on the device (dimE <= 1024) are in none of the
+ * three.  Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
+int PCGenEOGetCoarseBlockCounters(GENEO_PC pc, long long* blocked, long long* by_column, long long* host_blocks);
 
 /* ---- public counters / timers of geneoContext (hdr/geneo.hpp:96-123) ----------------------- */
 typedef struct {
@@ -451,11 +458,14 @@ int PCGenEOGetLocalSolverCounters(PC pc, long long* solves, long long* graph_lau
  * positive.  GeneoTestCoarseSolve: y <- (L L^T)^-1 y, `reps` >= 1 times from the same y (timing).  Every device buffer of
  * the hooks lies between canary pads and is read back: a write outside an array, a changed input or a HIP error is
  * reported.  nb == 0 runs the host code the PC uses without these kernels (host Cholesky; download, host sweeps, upload).
+ * GeneoTestCoarseSolveBlock: Y <- (L L^T)^-1 Y on the n x w row-major block Y (w = 16 | 32) by the blocked sweeps on
+ * blocks, `reps` >= 1 times from the same Y; Y holds the result of the last one.
  * Returns 0 ok, -1 error (PCGenEOGetError(NULL)), -3 the backend has no such kernels.
  * GeneoTestCoarseElapsed: milliseconds of the last factorisation and of one repetition of the last solve (device time
  * between two events; wall time for nb == 0; -1 before the first call). */
 int GeneoTestCoarseFactor(int n, int nb, const double* E, double* L, double* LT, int* status);
 int GeneoTestCoarseSolve(int n, int nb, const double* L, const double* LT, double* y, int reps);
+int GeneoTestCoarseSolveBlock(int n, int nb, int w, const double* L, const double* LT, double* Y, int reps);
 int GeneoTestCoarseElapsed(double* factor_ms, double* solve_ms);
 /* cg_start and `iters` steps [spmv, seg_pap, cg_update, cg_direction] of the batched CG on the matrix of `h`
  * (suboff[nsub] rows) with one chunk list alive across the sequence; caller_precond != 0: the form with dinv == NULL in
