@@ -100,6 +100,7 @@ SYMBOLS = {
     "KSPMatSolve_GenEO": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_int_p, c_dbl_p, c_int_p]),
     "PCGenEOGetBlockInfo": (C.c_int, [C.c_void_p, c_int_p] + [C.POINTER(C.c_longlong)] * 4),
     "PCGenEOGetCoarseBlockCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
+    "PCGenEOGetBlockKrylovInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 2),
     "PCGenEOGetInfo": (C.c_int, [C.c_void_p, C.POINTER(GeneoInfo)]),
     "PCGenEOGetEigenvalues": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
     "PCGenEOGetCandidates": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),

@@ -10,6 +10,11 @@
 //                             CU), lanes own two columns (one 16-byte load per block) and every (512 / W)-th row, LDS
 //                             reduction in index order, then one workgroup adds the partials in index order.  No atomics: the bits depend on n alone.
 //   k_axpy_cols / k_xpby_cols per-column coefficients from a device array, 16-byte accesses.
+//   k_gs_dots1 / k_gs_dots2   the Gram-Schmidt coefficients of a block GMRES step: k_coldot1 / k_coldot2 for up to BLOCK_GS_GROUP
+//                             left factors per pass over the right one (slab pointers from a device table), same bits per slab.
+//   k_gs_update               y <- y + sum_i c_i .* v_i in one pass, i in order, one rounded product and sum each (the bits of
+//                             successive k_axpy_cols), on k_coldot1's row ranges and lanes so that the squares of the result
+//                             can be summed in its order; k_scale_cols: out = c .* x.
 //   k_chol_solve_block        k_chol_solve (backend_hip.hip) with one workgroup per column of Y.
 // The elementwise kernels round every product and every sum (contraction off, as in cheb_dev.hip): the bits of the
 // composed forms in core.cpp and of the numpy expressions in the tests.  The triangular sweeps keep the compiler's
@@ -299,6 +304,218 @@ bool block_axpy_cols(double* Y, const double* X, const double* c, int n, int w) 
 }
 bool block_xpby_cols(double* P, const double* Z, const double* c, int n, int w) {
   return blk_cols<true>(P, Z, c, n, w, "block_xpby_cols");
+}
+
+// ---------------------------------------------------------------------------------------------- Gram-Schmidt on slabs
+// k_gs_dots1 is k_coldot1 with up to BLOCK_GS_GROUP left factors per pass over W: workgroup blockIdx.x takes the row range
+// k_coldot1 gives it, lane t the rows and the two columns k_coldot1 gives it, and every slab of the group (blockIdx.y) has
+// its own pair of accumulators, fed in row order with rounded products and sums: slab by slab the arithmetic of k_coldot1,
+// so the partials, and with k_gs_dots2 (= k_coldot2 per slab) the sums, have its bits.  The slab pointers come from a
+// device table; whether all of them allow 16-byte loads is decided here, once per workgroup (wave-uniform).
+template <int W, bool VEC>
+__device__ __forceinline__ void gs_dots_rows(const double* const (&vp)[BLOCK_GS_GROUP], int ng, const double* Wm, int lo,
+                                             int hi, int c, int rl, double (&a0)[BLOCK_GS_GROUP],
+                                             double (&a1)[BLOCK_GS_GROUP]) {
+  constexpr int R = 256 / (W / 2);
+  for (int i = lo + rl; i < hi; i += R) {
+    const int64_t e = (int64_t)i * W + 2 * c;
+    double w0, w1;
+    if (VEC) {
+      const blk_d2 wv = *reinterpret_cast<const blk_d2*>(Wm + e);
+      w0 = wv.x; w1 = wv.y;
+    } else {
+      w0 = Wm[e]; w1 = Wm[e + 1];
+    }
+#pragma unroll
+    for (int g = 0; g < BLOCK_GS_GROUP; ++g) {
+      if (g < ng) {                                  // (uniform)
+        double x0, x1;
+        if (VEC) {
+          const blk_d2 xv = *reinterpret_cast<const blk_d2*>(vp[g] + e);
+          x0 = xv.x; x1 = xv.y;
+        } else {
+          x0 = vp[g][e]; x1 = vp[g][e + 1];
+        }
+        a0[g] = __dadd_rn(a0[g], __dmul_rn(x0, w0));
+        a1[g] = __dadd_rn(a1[g], __dmul_rn(x1, w1));
+      }
+    }
+  }
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_gs_dots1(const double* const* __restrict__ V, int nb, const double* __restrict__ Wm,
+                                                  int n, int rows_per, double* __restrict__ work) {
+  constexpr int H = W / 2, R = 256 / H, G = BLOCK_GS_GROUP;
+  __shared__ double red[G][R][W];
+  const int t = threadIdx.x, c = t % H, rl = t / H;
+  const int lo = blockIdx.x * rows_per, hi = min(n, lo + rows_per);
+  const int i0 = blockIdx.y * G, ng = min(G, nb - i0);
+  const double* vp[G];
+  uintptr_t bits = reinterpret_cast<uintptr_t>(Wm);
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    vp[g] = V[i0 + min(g, ng - 1)];
+    bits |= reinterpret_cast<uintptr_t>(vp[g]);
+  }
+  double a0[G], a1[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) a0[g] = a1[g] = 0.0;
+  if ((bits & 15u) == 0) gs_dots_rows<W, true>(vp, ng, Wm, lo, hi, c, rl, a0, a1);
+  else gs_dots_rows<W, false>(vp, ng, Wm, lo, hi, c, rl, a0, a1);
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    red[g][rl][2 * c] = a0[g];
+    red[g][rl][2 * c + 1] = a1[g];
+  }
+  __syncthreads();
+  for (int e = t; e < ng * W; e += 256) {
+    const int g = e / W, j = e - g * W;
+    double s = red[g][0][j];
+    for (int r = 1; r < R; ++r) s = __dadd_rn(s, red[g][r][j]);
+    work[((int64_t)(i0 + g) * gridDim.x + blockIdx.x) * W + j] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_gs_dots2(const double* __restrict__ work, int nwg, int w, double* __restrict__ H) {
+  const int j = threadIdx.x, i = blockIdx.x;
+  if (j >= w) return;
+  double s = 0.0;
+  for (int g = 0; g < nwg; ++g) s = __dadd_rn(s, work[((int64_t)i * nwg + g) * w + j]);
+  H[(int64_t)i * w + j] = s;
+}
+
+bool block_gs_dots(const double* const* V, int nb, const double* Wm, int n, int w, double* H, double* work) {
+  if (w != 16 && w != 32) throw std::runtime_error("block_gs_dots: width is not 16 or 32");
+  if (nb < 0 || n < 0 || (nb > 0 && (!V || !Wm || !H || !work))) throw std::runtime_error("block_gs_dots: bad argument");
+  if (nb == 0) return true;
+  hipStream_t s = (hipStream_t)get_stream();
+  const int nwg = block_coldot_nwg(n), rows_per = block_coldot_rows_per(n);
+  const dim3 grid(nwg, (nb + BLOCK_GS_GROUP - 1) / BLOCK_GS_GROUP);
+  if (w == 16) hipLaunchKernelGGL((k_gs_dots1<16>), grid, dim3(256), 0, s, V, nb, Wm, n, rows_per, work);
+  else hipLaunchKernelGGL((k_gs_dots1<32>), grid, dim3(256), 0, s, V, nb, Wm, n, rows_per, work);
+  hipLaunchKernelGGL(k_gs_dots2, dim3(nb), dim3(64), 0, s, work, nwg, w, H);
+  HIPCHK(hipGetLastError());
+  return true;
+}
+
+// k_gs_update: y <- fl(y + fl(c_i v_i)), i = 0 .. nb - 1 in that order, on the entries a lane of k_coldot1 owns, so that
+// the squares of the result can be summed in its order (NORM): the partials of block_coldot(Y', Y').  The coefficients of
+// a launch (at most BLK_GS_NBMAX slabs; the wrapper splits longer lists) sit in LDS.
+constexpr int BLK_GS_NBMAX = 64;
+
+template <int W, bool NORM, bool VEC>
+__device__ __forceinline__ void gs_update_rows(double* Y, const double* const* __restrict__ V, int nb, const double* cs, int lo,
+                                               int hi, int c, int rl, double& a0, double& a1) {
+  constexpr int R = 256 / (W / 2);
+  for (int i = lo + rl; i < hi; i += R) {
+    const int64_t e = (int64_t)i * W + 2 * c;
+    double y0, y1;
+    if (VEC) {
+      const blk_d2 yv = *reinterpret_cast<const blk_d2*>(Y + e);
+      y0 = yv.x; y1 = yv.y;
+    } else {
+      y0 = Y[e]; y1 = Y[e + 1];
+    }
+#pragma unroll 4
+    for (int k = 0; k < nb; ++k) {
+      const double* v = V[k];
+      double x0, x1;
+      if (VEC) {
+        const blk_d2 xv = *reinterpret_cast<const blk_d2*>(v + e);
+        x0 = xv.x; x1 = xv.y;
+      } else {
+        x0 = v[e]; x1 = v[e + 1];
+      }
+      y0 = __dadd_rn(y0, __dmul_rn(cs[k * W + 2 * c], x0));
+      y1 = __dadd_rn(y1, __dmul_rn(cs[k * W + 2 * c + 1], x1));
+    }
+    if (VEC) {
+      *reinterpret_cast<blk_d2*>(Y + e) = blk_d2{y0, y1};
+    } else {
+      Y[e] = y0; Y[e + 1] = y1;
+    }
+    if (NORM) {
+      a0 = __dadd_rn(a0, __dmul_rn(y0, y0));
+      a1 = __dadd_rn(a1, __dmul_rn(y1, y1));
+    }
+  }
+}
+
+template <int W, bool NORM>
+__global__ __launch_bounds__(256) void k_gs_update(double* Y, const double* const* __restrict__ V, int nb,
+                                                   const double* __restrict__ C, int n, int rows_per, double* work) {
+  constexpr int H = W / 2, R = 256 / H;
+  __shared__ double cs[BLK_GS_NBMAX * W];
+  __shared__ double red[R][W];
+  const int t = threadIdx.x, c = t % H, rl = t / H;
+  const int lo = blockIdx.x * rows_per, hi = min(n, lo + rows_per);
+  for (int e = t; e < nb * W; e += 256) cs[e] = C[e];
+  uintptr_t bits = reinterpret_cast<uintptr_t>(Y);
+  for (int k = 0; k < nb; ++k) bits |= reinterpret_cast<uintptr_t>(V[k]);
+  __syncthreads();
+  double a0 = 0.0, a1 = 0.0;
+  if ((bits & 15u) == 0) gs_update_rows<W, NORM, true>(Y, V, nb, cs, lo, hi, c, rl, a0, a1);
+  else gs_update_rows<W, NORM, false>(Y, V, nb, cs, lo, hi, c, rl, a0, a1);
+  if (NORM) {
+    red[rl][2 * c] = a0;
+    red[rl][2 * c + 1] = a1;
+    __syncthreads();
+    if (t < W) {
+      double s = red[0][t];
+      for (int r = 1; r < R; ++r) s = __dadd_rn(s, red[r][t]);
+      work[(int64_t)blockIdx.x * W + t] = s;
+    }
+  }
+}
+
+bool block_gs_update(double* Y, const double* const* V, int nb, const double* C, int n, int w, double* norm2, double* work) {
+  if (w != 16 && w != 32) throw std::runtime_error("block_gs_update: width is not 16 or 32");
+  if (nb < 0 || n < 0 || !Y || (nb > 0 && (!V || !C)) || (norm2 && !work)) throw std::runtime_error("block_gs_update: bad argument");
+  if (nb == 0) return norm2 ? block_coldot(Y, Y, n, w, norm2, work) : true;
+  hipStream_t s = (hipStream_t)get_stream();
+  const int nwg = block_coldot_nwg(n), rows_per = block_coldot_rows_per(n);
+  for (int k0 = 0; k0 < nb; k0 += BLK_GS_NBMAX) {
+    const int nk = std::min(BLK_GS_NBMAX, nb - k0);
+    const bool norm = norm2 && k0 + nk == nb;         // the squares of the final values alone
+    const double* const* Vk = V + k0;
+    const double* Ck = C + (size_t)k0 * w;
+#define BLK_UPD(W_, N_) hipLaunchKernelGGL((k_gs_update<W_, N_>), dim3(nwg), dim3(256), 0, s, Y, Vk, nk, Ck, n, rows_per, work)
+    if (w == 16) { if (norm) BLK_UPD(16, true); else BLK_UPD(16, false); }
+    else { if (norm) BLK_UPD(32, true); else BLK_UPD(32, false); }
+#undef BLK_UPD
+  }
+  if (norm2) hipLaunchKernelGGL(k_coldot2, dim3(1), dim3(64), 0, s, work, nwg, w, norm2);
+  HIPCHK(hipGetLastError());
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_scale_cols(double* Out, const double* X, const double* __restrict__ c, int64_t tot,
+                                                    int w, int vec) {
+  const int64_t gs = (int64_t)gridDim.x * blockDim.x, g0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (!vec) {
+    for (int64_t e = g0; e < tot; e += gs) Out[e] = __dmul_rn(c[e & (w - 1)], X[e]);
+    return;
+  }
+  for (int64_t p = g0; p < (tot >> 1); p += gs) {  // tot = n w is even; both entries lie in one row
+    const int64_t e = 2 * p;
+    const int j = (int)(e & (w - 1));
+    const blk_d2 xv = *reinterpret_cast<const blk_d2*>(X + e);
+    *reinterpret_cast<blk_d2*>(Out + e) = blk_d2{__dmul_rn(c[j], xv.x), __dmul_rn(c[j + 1], xv.y)};
+  }
+}
+
+bool block_scale_cols(double* Out, const double* X, const double* c, int n, int w) {
+  if (w != 16 && w != 32) throw std::runtime_error("block_scale_cols: width is not 16 or 32");
+  if (n <= 0) return true;
+  if (!Out || !X || !c) throw std::runtime_error("block_scale_cols: null argument");
+  const int64_t tot = (int64_t)n * w;
+  const int vec = blk_al16(Out) && blk_al16(X) ? 1 : 0;
+  const int64_t work = vec ? tot / 2 : tot;
+  const int grid = (int)std::min<int64_t>((work + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_scale_cols, dim3(grid), dim3(256), 0, (hipStream_t)get_stream(), Out, X, c, tot, w, vec);
+  HIPCHK(hipGetLastError());
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------- coarse solve, w columns

@@ -156,6 +156,7 @@ const char* PCGenEOGetOptionsString(PC pc) {
            o.ksp_restart, o.dls1_ksp.c_str(), o.dls1_cheb_esteig_its, o.dls1_cheb_safety_lo, o.dls1_cheb_safety_hi,
            o.block_width);
   pc->optstr = buf;
+  if (!o.ksp_matsolve_type.empty()) pc->optstr += ";ksp_matsolve_type=" + o.ksp_matsolve_type;   // only when set
   return pc->optstr.c_str();
 }
 const char* PCGenEOGetError(PC pc) { return pc ? pc->err.c_str() : g_global_err.c_str(); }
@@ -207,7 +208,9 @@ const char* usageGenEO_c(void) {
          "  -dls1_amg_strength T / -els2_amg_strength T   aggregation from level 1 on ties |a_ij| >= T 0.5^l sqrt(a_ii a_jj) only\n"
          "  -amg_coarse_size / -amg_smooth_degree / -amg_smooth_ratio / -amg_max_levels\n"
          "  -dls1_amg_smooth_ratio R / -els2_amg_smooth_ratio R   the smoothing interval [rho / R, 1.1 rho] per hierarchy\n"
-         "  -ksp_type cg|gmres -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n\n";
+         "  -ksp_type cg|gmres -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n"
+         "  -ksp_matsolve_type cg|gmres   the Krylov method of KSPMatSolve_GenEO alone (unset: -ksp_type, which must then be cg);\n"
+         "                   gmres: restarted GMRES on every column in lock step, for the non-symmetric modes (RAS, ORAS, hybrid)\n\n";
 }
 
 PetscErrorCode PCSetOperators_GenEO(PC pc, const GeneoMatIS* A) {
@@ -394,6 +397,11 @@ PetscErrorCode KSPMatSolve_GenEO(PC pc, const double* B, int ldb, double* X, int
 int PCGenEOGetBlockInfo(PC pc, int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) {
   if (!pc || !pc->ctx) return -1;
   pc->ctx->block_info(width, slabs, columns, padded, graph_launches);
+  return 0;
+}
+int PCGenEOGetBlockKrylovInfo(PC pc, int* basis_slabs, double* basis_bytes, long long* gs_fused, long long* gs_composed) {
+  if (!pc || !pc->ctx) return -1;
+  pc->ctx->block_krylov_info(basis_slabs, basis_bytes, gs_fused, gs_composed);
   return 0;
 }
 int PCGenEOGetCoarseBlockCounters(PC pc, long long* blocked, long long* by_column, long long* host_blocks) {
@@ -994,7 +1002,8 @@ int GeneoTestPrimitive(const char* name, const int* I, const double* D, void* co
   return rc;
 }
 
-// ---- test hook of the block primitives (block_dev.h; argument table: tests/block_rhs_util.py) ---------------------------
+// ---- test hook of the block primitives (block_dev.h; argument tables: tests/block_rhs_util.py, and
+// tests/block_gmres_util.py for block_gs_dots, block_gs_update, block_scale_cols and block_gs_group) ----------------------
 // As GeneoTestPrimitive: unpack, call, leave the results where the primitive wrote them.  "block_fused" 0 runs the composed
 // forms of core.cpp instead.  Returns 0 / 1 (the primitive's bool), -1 on an exception, -2 for an unknown name.
 int GeneoTestBlockPrimitive(const char* name, const int* I, const double* D, void* const* P) {
@@ -1037,6 +1046,17 @@ int GeneoTestBlockPrimitive(const char* name, const int* I, const double* D, voi
     } else if (k == "block_xpby_cols") {
       rc = (fused ? bk::block_xpby_cols(d(0), d(1), d(2), I[0], I[1])
                   : geneo::block_xpby_cols_composed_once(d(0), d(1), d(2), I[0], I[1])) ? 1 : 0;
+    } else if (k == "block_gs_group") {                // the group size of bk::block_gs_dots, as the return value
+      rc = bk::BLOCK_GS_GROUP;
+    } else if (k == "block_gs_dots") {                 // I(nb, n, w)  P(V table, W, H, work)
+      rc = (fused ? bk::block_gs_dots((const double* const*)P[0], I[0], d(1), I[1], I[2], d(2), d(3))
+                  : geneo::block_gs_dots_composed_once((const double* const*)P[0], I[0], d(1), I[1], I[2], d(2), d(3))) ? 1 : 0;
+    } else if (k == "block_gs_update") {               // I(nb, n, w)  P(Y, V table, C, norm2 | NULL, work | NULL)
+      rc = (fused ? bk::block_gs_update(d(0), (const double* const*)P[1], I[0], d(2), I[1], I[2], d(3), d(4))
+                  : geneo::block_gs_update_composed_once(d(0), (const double* const*)P[1], I[0], d(2), I[1], I[2], d(3), d(4))) ? 1 : 0;
+    } else if (k == "block_scale_cols") {              // I(n, w)  P(Out, X, c)
+      rc = (fused ? bk::block_scale_cols(d(0), d(1), d(2), I[0], I[1])
+                  : geneo::block_scale_cols_composed_once(d(0), d(1), d(2), I[0], I[1])) ? 1 : 0;
     } else if (k == "chol_solve_block") {
       rc = (fused ? bk::chol_solve_block(d(0), d(1), I[0], d(2), I[1])
                   : geneo::chol_solve_block_composed_once(d(0), d(1), I[0], d(2), I[1])) ? 1 : 0;

@@ -39,6 +39,7 @@
 #include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "dense.h"
+#include "gmres_col.h"
 
 // A backend without the blocked coarse kernels (coarse_dev.h) links these: "not available", nothing touched.  The HIP
 // object's definitions take their place in the product library.
@@ -199,6 +200,45 @@ bool block_xpby_cols_composed_once(double* P, const double* Z, const double* c, 
   bk::sync();
   return true;
 }
+// The Gram-Schmidt passes of the block GMRES from bk::block_coldot and bk::block_axpy_cols, one call per basis slab: what
+// bk::block_gs_dots and bk::block_gs_update promise the bits of.  Vh: the slab pointers on the HOST.
+bool block_gs_dots_composed(const double* const* Vh, int nb, const double* W, int n, int w, double* H, double* work) {
+  for (int i = 0; i < nb; ++i) bk::block_coldot(Vh[i], W, n, w, H + (size_t)i * w, work);
+  return true;
+}
+bool block_gs_update_composed(double* Y, const double* const* Vh, int nb, const double* C, int n, int w, double* norm2,
+                              double* work) {
+  for (int i = 0; i < nb; ++i) bk::block_axpy_cols(Y, Vh[i], C + (size_t)i * w, n, w);
+  if (norm2) bk::block_coldot(Y, Y, n, w, norm2, work);
+  return true;
+}
+// the _once forms take the pointer table from the device, as the kernels do
+static std::vector<const double*> table_download(const double* const* V, int nb) {
+  std::vector<const double*> h(std::max(0, nb));
+  if (nb > 0) bk::d2h(h.data(), V, sizeof(double*) * (size_t)nb);
+  return h;
+}
+bool block_gs_dots_composed_once(const double* const* V, int nb, const double* W, int n, int w, double* H, double* work) {
+  const std::vector<const double*> h = table_download(V, nb);
+  const bool ok = block_gs_dots_composed(h.data(), nb, W, n, w, H, work);
+  bk::sync();
+  return ok;
+}
+bool block_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, int w, double* norm2,
+                                   double* work) {
+  const std::vector<const double*> h = table_download(V, nb);
+  const bool ok = block_gs_update_composed(Y, h.data(), nb, C, n, w, norm2, work);
+  bk::sync();
+  return ok;
+}
+bool block_scale_cols_composed_once(double* Out, const double* X, const double* c, int n, int w) {
+  if (n <= 0) return true;
+  OnceBufs b;
+  if (Out != X) bk::copy(Out, X, slab_entries(n, w));
+  bk::block_colscale(b.rows(n), Out, w, w, c);
+  bk::sync();
+  return true;
+}
 bool chol_solve_block_composed_once(const double* L, const double* LT, int n, double* Y, int w) {
   if (n <= 0) return true;
   if (n > 1024) return false;
@@ -242,6 +282,17 @@ __attribute__((weak)) bool block_xpby_cols(double* P, const double* Z, const dou
 }
 __attribute__((weak)) bool chol_solve_block(const double* L, const double* LT, int n, double* Y, int w) {
   return geneo::chol_solve_block_composed_once(L, LT, n, Y, w);
+}
+__attribute__((weak)) bool block_gs_dots(const double* const* V, int nb, const double* W, int n, int w, double* H,
+                                         double* work) {
+  return geneo::block_gs_dots_composed_once(V, nb, W, n, w, H, work);
+}
+__attribute__((weak)) bool block_gs_update(double* Y, const double* const* V, int nb, const double* C, int n, int w,
+                                           double* norm2, double* work) {
+  return geneo::block_gs_update_composed_once(Y, V, nb, C, n, w, norm2, work);
+}
+__attribute__((weak)) bool block_scale_cols(double* Out, const double* X, const double* c, int n, int w) {
+  return geneo::block_scale_cols_composed_once(Out, X, c, n, w);
 }
 }  // namespace bk
 
@@ -426,6 +477,11 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
   if (key == "-ksp_type") {
     if (value != "cg" && value != "gmres") return "unsupported -ksp_type " + value;
     o.ksp_type = value;
+    return "";
+  }
+  if (key == "-ksp_matsolve_type") {
+    if (value != "cg" && value != "gmres") return "unsupported -ksp_matsolve_type " + value;
+    o.ksp_matsolve_type = value;
     return "";
   }
   if (key == "-ksp_rtol") return dbl(o.ksp_rtol);
@@ -1971,6 +2027,13 @@ void PC::block_release() {
   blk_yE = blk_G = blk_C = blk_ZR = blk_col = blk_dots = blk_dotwork = blk_coef = nullptr;
   blk_g2e = blk_e2c = nullptr;
   blk_work.release();
+  for (double* p : blk_basis) bk::dfree(p);
+  blk_basis.clear();
+  for (void* p : {(void*)blk_basis_tab, (void*)blk_gs_h, (void*)blk_gs_c, (void*)blk_gs_work}) bk::dfree(p);
+  blk_basis_tab = nullptr;
+  blk_gs_h = blk_gs_c = blk_gs_work = nullptr;
+  blk_gs_bytes = 0.0;
+  blk_gs_fused = blk_gs_composed = 0;
   blk_w = blk_kp = 0;
   blk_slabs = blk_columns = blk_padded = 0;
   coarse_blk_blocked = coarse_blk_by_column = coarse_blk_host = 0;
@@ -2033,6 +2096,13 @@ void PC::block_info(int* width, long long* slabs, long long* columns, long long*
   if (columns) *columns = blk_columns;
   if (padded) *padded = blk_padded;
   if (graph_launches) *graph_launches = blk_chain.replays;
+}
+
+void PC::block_krylov_info(int* basis_slabs, double* basis_bytes, long long* gs_fused, long long* gs_composed) const {
+  if (basis_slabs) *basis_slabs = (int)blk_basis.size();
+  if (basis_bytes) *basis_bytes = blk_gs_bytes;
+  if (gs_fused) *gs_fused = blk_gs_fused;
+  if (gs_composed) *gs_composed = blk_gs_composed;
 }
 
 void PC::coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const {
@@ -4260,18 +4330,193 @@ int PC::solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int*
   return 0;
 }
 
+// The basis of the block GMRES: `slabs` owned slabs, their pointer table on the device, and the coefficient and partial-sum
+// buffers of the two Gram-Schmidt passes sized for that many.  Grown step by step, as solve_gmres grows V; kept for the next
+// solve; freed by block_release.  (Every step ends in a download, so nothing is in flight when a buffer is replaced.)
+void PC::basis_grow(int slabs) {
+  if ((int)blk_basis.size() >= slabs) return;
+  const int n = n_owned(), w = blk_w;
+  const size_t nw = (size_t)slab_entries(n, w);
+  while ((int)blk_basis.size() < slabs) blk_basis.push_back((double*)bk::alloc(sizeof(double) * std::max<size_t>(1, nw)));
+  for (void* p : {(void*)blk_basis_tab, (void*)blk_gs_h, (void*)blk_gs_c, (void*)blk_gs_work}) bk::dfree(p);
+  const size_t work = (size_t)bk::block_coldot_nwg(n) * slabs * w;
+  blk_basis_tab = (double**)bk::alloc(sizeof(double*) * slabs);
+  blk_gs_h = (double*)bk::alloc(sizeof(double) * (size_t)slabs * w);
+  blk_gs_c = (double*)bk::alloc(sizeof(double) * (size_t)slabs * w);
+  blk_gs_work = (double*)bk::alloc(sizeof(double) * work);
+  bk::h2d(blk_basis_tab, blk_basis.data(), sizeof(double*) * slabs);
+  blk_gs_bytes = (double)(sizeof(double) * ((size_t)slabs * nw + 2 * (size_t)slabs * w + work) + sizeof(double*) * slabs);
+}
+
+// solve_gmres on every column of a block, in lock step, zero initial guess: left preconditioning, classical Gram-Schmidt,
+// Givens residual.  Step k takes all k + 1 coefficients of all columns from one pass (bk::block_gs_dots) and one
+// all-reduce of (k + 1) w values, and the projection with the norms of the remainder from a second pass
+// (bk::block_gs_update) and an all-reduce of w.  Every column has its own Hessenberg system and ConvTest on the host
+// (GmresColumn); all share the step index and the restart boundary.  A column that met its test (or whose remainder or
+// restart residual is exactly 0) is frozen: its its / rnorm / reason are those of that moment, its y is solved at once, and
+// the coefficient that scales its next basis column is exactly 0 -- from then on its basis columns, dots and updates are
+// exact zeros, in this cycle and (the start column scaled by 0) in every later one.
+int PC::solve_gmres_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason) {
+  const int n = n_owned(), w = blk_w, nw = slab_entries(n, w);
+  const int mr = std::max(1, opt.ksp_restart);
+  DeviceVectors bufs;
+  auto dv = [&](void) { return bufs.get(nw); };
+  double *b = dv(), *x = dv(), *t = dv(), *wv = dv();
+  std::vector<double> hd((size_t)(mr + 1) * w), hc((size_t)(mr + 1) * w), nrm(w), sc(w);
+  std::vector<GmresColumn> col(w);
+  for (GmresColumn& c : col) c.init(mr);
+  auto applied = [&](int ms) {
+    blk_slabs += 1;
+    blk_columns += ms;
+    blk_padded += w - ms;
+  };
+  auto coldot = [&](const double* P, const double* Q, double* h_out) {     // the kernel's bits under either variant
+    bk::block_coldot(P, Q, n, w, blk_dots, blk_dotwork);
+    allreduce(blk_dots, w);
+    bk::d2h(h_out, blk_dots, sizeof(double) * w);
+  };
+  auto scale = [&](double* Out, const double* P) {                        // Out[:, j] = sc[j] P[:, j]
+    bk::h2d(blk_coef, sc.data(), sizeof(double) * w);
+    if (g_block_fused.load()) bk::block_scale_cols(Out, P, blk_coef, n, w);
+    else block_scale_cols_composed_once(Out, P, blk_coef, n, w);
+  };
+  auto update = [&](double* Y, int nb, bool norms) {                      // Y += sum_i hc[i] .* V_i, squares into nrm
+    bk::h2d(blk_gs_c, hc.data(), sizeof(double) * (size_t)nb * w);
+    double* n2 = norms ? blk_dots : nullptr;
+    if (g_block_fused.load()) {
+      bk::block_gs_update(Y, blk_basis_tab, nb, blk_gs_c, n, w, n2, blk_dotwork);
+      ++blk_gs_fused;
+    } else {
+      block_gs_update_composed(Y, blk_basis.data(), nb, blk_gs_c, n, w, n2, blk_dotwork);
+      ++blk_gs_composed;
+    }
+    if (!norms) return;
+    allreduce(blk_dots, w);
+    bk::d2h(nrm.data(), blk_dots, sizeof(double) * w);
+  };
+  for (int j0 = 0; j0 < m; j0 += w) {
+    const int ms = std::min(w, m - j0);
+    std::vector<ConvTest> conv(ms, ConvTest{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol});
+    std::vector<char> frozen(w, 1);          // the padding columns never take part
+    int* it = its + j0;
+    double* rn = rnorm + j0;
+    int* rs = reason + j0;
+    slab_in(B + (size_t)j0 * ldb, ldb, ms, b);
+    bk::zero(x, sizeof(double) * (size_t)nw);
+    int active = 0, steps = 0;               // steps: the iteration count of every column that is still active
+    bool first = true;
+    while (true) {
+      basis_grow(1);
+      double* V0 = blk_basis[0];
+      if (first) {
+        apply_on(slab, b, V0);                // x = 0: r = M^-1 b
+      } else {
+        matmult(x, t, w, slab.wl, slab.xe, slab.ye);
+        bk::axpby(t, 1.0, b, -1.0, nw);
+        apply_on(slab, t, V0);
+      }
+      applied(ms);
+      coldot(V0, V0, nrm.data());
+      for (int j = 0; j < w; ++j) {
+        sc[j] = 0.0;
+        col[j].start(0.0);
+        if (j >= ms) continue;
+        const double r0 = std::sqrt(nrm[j]);
+        if (first) {
+          it[j] = 0;
+          rn[j] = r0;
+          rs[j] = conv[j](0, r0, -1.0);
+          frozen[j] = rs[j] != 0;
+          active += !frozen[j];
+        }
+        if (frozen[j]) continue;
+        if (r0 == 0.0) {
+          rs[j] = 3;
+          frozen[j] = 1;
+          --active;
+          continue;
+        }
+        col[j].start(r0);
+        sc[j] = 1.0 / r0;
+      }
+      first = false;
+      if (active == 0) break;
+      scale(V0, V0);
+      int k = 0;
+      while (k < mr && steps < opt.ksp_max_it && active > 0) {
+        basis_grow(k + 2);
+        matmult(blk_basis[k], t, w, slab.wl, slab.xe, slab.ye);
+        apply_on(slab, t, wv);
+        applied(ms);
+        const int nb = k + 1;
+        if (g_block_fused.load()) {
+          bk::block_gs_dots(blk_basis_tab, nb, wv, n, w, blk_gs_h, blk_gs_work);
+          ++blk_gs_fused;
+        } else {
+          block_gs_dots_composed(blk_basis.data(), nb, wv, n, w, blk_gs_h, blk_gs_work);
+          ++blk_gs_composed;
+        }
+        allreduce(blk_gs_h, nb * w);
+        bk::d2h(hd.data(), blk_gs_h, sizeof(double) * (size_t)nb * w);
+        for (int e = 0; e < nb * w; ++e) hc[e] = -hd[e];
+        update(wv, nb, true);
+        ++steps;
+        for (int j = 0; j < w; ++j) {
+          sc[j] = 0.0;
+          if (frozen[j]) continue;
+          const double hn = std::sqrt(nrm[j]);
+          const double r = col[j].step(hd.data() + j, (size_t)w, hn);
+          it[j] = steps;
+          rn[j] = r;
+          rs[j] = conv[j](steps, r, -1.0);
+          if (!rs[j] && hn == 0.0) rs[j] = 3;           // no next direction: the Krylov space is exhausted
+          if (rs[j]) {
+            col[j].solve();
+            frozen[j] = 1;
+            --active;
+          } else {
+            sc[j] = 1.0 / hn;
+          }
+        }
+        scale(blk_basis[k + 1], wv);
+        ++k;
+      }
+      // x += sum_i y_i v_i: the columns still active solve their k x k system now, the others did when they froze
+      for (int j = 0; j < w; ++j) {
+        if (!frozen[j]) col[j].solve();
+        for (int i = 0; i < k; ++i) hc[(size_t)i * w + j] = col[j].y[i];
+      }
+      if (k > 0) update(x, k, false);
+      if (steps >= opt.ksp_max_it) {
+        for (int j = 0; j < ms; ++j)
+          if (!frozen[j]) {
+            rs[j] = -3;
+            frozen[j] = 1;
+            --active;
+          }
+      }
+      if (active == 0) break;
+    }
+    slab_out(x, ms, X + (size_t)j0 * ldx, ldx);
+  }
+  return 0;
+}
+
 int PC::solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason) {
   if (int rc = block_check("KSPMatSolve_GenEO", std::min(ldb, ldx), m, B, X)) return rc;
   if (!its || !rnorm || !reason) return fail("KSPMatSolve_GenEO: its, rnorm and reason need m entries each");
-  if (opt.ksp_type != "cg")
-    return fail("KSPMatSolve_GenEO: -ksp_type " + opt.ksp_type + " has no block form (the block Krylov method is -ksp_type cg)");
+  const std::string& method = opt.ksp_matsolve_type.empty() ? opt.ksp_type : opt.ksp_matsolve_type;
+  if (opt.ksp_matsolve_type.empty() && method != "cg")
+    return fail("KSPMatSolve_GenEO: -ksp_type " + opt.ksp_type + " has no block form (the block Krylov method is -ksp_type cg; "
+                "-ksp_matsolve_type gmres selects block GMRES for the block solve alone)");
   if (opt.ksp_guess_nonzero)
     return fail("KSPMatSolve_GenEO: -ksp_initial_guess_nonzero is not supported (the block solve starts from zero: "
                 "-ksp_initial_guess_nonzero 0)");
   auto t0 = clk::now();
   int rc = 0;
   try {
-    rc = solve_cg_block(B, ldb, X, ldx, m, its, rnorm, reason);
+    rc = method == "gmres" ? solve_gmres_block(B, ldb, X, ldx, m, its, rnorm, reason)
+                           : solve_cg_block(B, ldb, X, ldx, m, its, rnorm, reason);
   } catch (std::exception& e) {
     return fail(e.what());
   }

@@ -105,6 +105,8 @@ struct Options {
   bool dls1_amg_single = true;   // -dls1_amg_precision single|double: storage of the level matrices the V-cycle of the local solves reads
   // Krylov driver (counterpart of the PETSc KSP the reference calls at driver:1240)
   std::string ksp_type = "gmres";
+  // -ksp_matsolve_type cg|gmres: the Krylov method of KSPMatSolve_GenEO alone; unset (empty): -ksp_type, which must be cg
+  std::string ksp_matsolve_type;
   double ksp_rtol = 1e-5, ksp_atol = 1e-50, ksp_dtol = 1e5;
   int ksp_max_it = 10000, ksp_restart = 30;
   bool ksp_guess_nonzero = true;   // driver:1348 always sets it
@@ -140,6 +142,15 @@ bool block_coldot_composed_once(const double* X, const double* Y, int n, int w, 
 bool block_axpy_cols_composed_once(double* Y, const double* X, const double* c, int n, int w);
 bool block_xpby_cols_composed_once(double* P, const double* Z, const double* c, int n, int w);
 bool chol_solve_block_composed_once(const double* L, const double* LT, int n, double* Y, int w);
+// the Gram-Schmidt passes of the block GMRES, one bk::block_coldot / bk::block_axpy_cols per basis slab (Vh: slab pointers
+// on the host); the _once forms read the pointer table from the device, as bk::block_gs_dots / _update do, and wait
+bool block_gs_dots_composed(const double* const* Vh, int nb, const double* W, int n, int w, double* H, double* work);
+bool block_gs_update_composed(double* Y, const double* const* Vh, int nb, const double* C, int n, int w, double* norm2,
+                              double* work);
+bool block_gs_dots_composed_once(const double* const* V, int nb, const double* W, int n, int w, double* H, double* work);
+bool block_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, int w, double* norm2,
+                                   double* work);
+bool block_scale_cols_composed_once(double* Out, const double* X, const double* c, int n, int w);
 
 struct Info {                 // public counters / timers of geneoContext (hdr/geneo.hpp:96-123)
   int estimDimELoc = 0, realDimELoc = 0, nicolaidesLoc = 0, dimE = 0;
@@ -215,11 +226,16 @@ class PC {
   // processed in slabs of the width (the last one zero-padded).  Each returns an error for a set-up without a width.
   int apply_mat(const double* X, int ldx, double* Y, int ldy, int m);        // PCMatApply: Y = M^-1 X
   int matmult_mat(const double* X, int ldx, double* Y, int ldy, int m);      // MatMatMult: Y = A X
-  // KSPMatSolve: PCG on every column in lock step, zero initial guess (X is zeroed here); its / rnorm / reason: m entries
+  // KSPMatSolve: PCG (or, -ksp_matsolve_type gmres, restarted GMRES) on every column in lock step, zero initial guess (X is
+  // zeroed here); its / rnorm / reason: m entries
   int solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
   // since the set-up: slabs applied by apply_mat (KSPMatSolve's included), their columns, the zero columns that padded
   // them, and the local solves of slabs replayed from the HIP graph (the others went out as direct launches)
   void block_info(int* width, long long* slabs, long long* columns, long long* padded, long long* graph_launches) const;
+  // block GMRES (PCGenEOGetBlockKrylovInfo): basis slabs held and the bytes of the basis with its tables and partial sums
+  // (0 before the first block GMRES solve of a set-up), and since the set-up the Gram-Schmidt passes that went through
+  // bk::block_gs_dots / bk::block_gs_update and through their composed forms
+  void block_krylov_info(int* basis_slabs, double* basis_bytes, long long* gs_fused, long long* gs_composed) const;
   // since the set-up: slab applications of E^-1 by the blocked block sweeps (bk::coarse_solve_block), column by column
   // through the single-vector path, and by one host round trip of the whole block (PCGenEOGetCoarseBlockCounters)
   void coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const;
@@ -351,6 +367,15 @@ class PC {
   void slab_coldot(const double* X, const double* Y, double* h_out);
   void slab_cols(bool xpby, double* A, const double* B, const double* h_c);
   int solve_cg_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
+  // block GMRES: the basis slabs with their device pointer table, dots / coefficients (slabs x w each) and the partial sums
+  // of bk::block_gs_dots; allocated by the first block GMRES solve, grown as the steps need them, freed by block_release
+  std::vector<double*> blk_basis;
+  double** blk_basis_tab = nullptr;
+  double *blk_gs_h = nullptr, *blk_gs_c = nullptr, *blk_gs_work = nullptr;
+  double blk_gs_bytes = 0.0;
+  long long blk_gs_fused = 0, blk_gs_composed = 0;
+  void basis_grow(int slabs);
+  int solve_gmres_block(const double* B, int ldb, double* X, int ldx, int m, int* its, double* rnorm, int* reason);
   HostCsr host_neu_cache, host_dir_cache;   // block-diagonal host copies of A_Neu / the level-1 matrix, reused by the next set-up
   AmgDevice* amg1 = nullptr;   // hierarchy of the level-1 (Dirichlet / Robin) block-diagonal matrix (local solves)
   AmgDevice* amgN = nullptr;   // hierarchy of the Neumann block-diagonal matrix (LOBPCG preconditioner)

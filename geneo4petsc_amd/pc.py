@@ -101,7 +101,7 @@ class GenEOPC:
         out = {}
         for kv in self.lib.PCGenEOGetOptionsString(self.h).decode().split(";"):
             k, _, v = kv.partition("=")
-            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type"):
+            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type", "ksp_matsolve_type"):
                 out[k] = v
             elif k == "dls1_cheb_safety":
                 out[k] = tuple(float(t) for t in v.split(","))
@@ -268,7 +268,7 @@ class GenEOPC:
         return self._block(lambda xd, yd, n, m: self._chk(self.lib.MatMatMult_GenEO(self.h, xd.ptr, n, yd.ptr, n, m)), X)
 
     def mat_solve(self, B):
-        """KSPMatSolve_GenEO: block PCG from a zero initial guess.  Returns (X, its, rnorm, reasons) with one entry per
+        """KSPMatSolve_GenEO: block PCG (or, -ksp_matsolve_type gmres, block GMRES) from a zero initial guess.  Returns (X, its, rnorm, reasons) with one entry per
         column; reasons are the KSPConvergedReason names."""
         def run(bd, xd, n, m):
             its, rs, rn = np.zeros(max(1, m), dtype=np.int32), np.zeros(max(1, m), dtype=np.int32), np.zeros(max(1, m))
@@ -285,6 +285,15 @@ class GenEOPC:
         if self.lib.PCGenEOGetBlockInfo(self.h, C.byref(w), *[C.byref(x) for x in v]) < 0:
             raise GenEOError("PCGenEOGetBlockInfo: bad handle")
         return dict(width=w.value, slabs=v[0].value, columns=v[1].value, padded=v[2].value, graph_launches=v[3].value)
+
+    def block_krylov_info(self):
+        """PCGenEOGetBlockKrylovInfo: basis slabs and device bytes the block GMRES (-ksp_matsolve_type gmres) holds now, and
+        since the set-up its Gram-Schmidt passes through the fused kernels and through their composed forms."""
+        s, b = C.c_int(0), C.c_double(0.0)
+        v = [C.c_longlong(0) for _ in range(2)]
+        if self.lib.PCGenEOGetBlockKrylovInfo(self.h, C.byref(s), C.byref(b), *[C.byref(x) for x in v]) < 0:
+            raise GenEOError("PCGenEOGetBlockKrylovInfo: bad handle")
+        return dict(basis_slabs=s.value, basis_bytes=b.value, gs_fused=v[0].value, gs_composed=v[1].value)
 
     def coarse_block_counters(self):
         """PCGenEOGetCoarseBlockCounters since the set-up: slab applications of E^-1 by the blocked sweeps on the whole block,

@@ -197,8 +197,17 @@ int PCGenEOGetResidualHistory(GENEO_PC pc, double* hist, int cap);
  * operators; under -dls1_amg_precision double they differ by summation order alone.
  * KSPMatSolve_GenEO: preconditioned CG on every column in lock step with a zero initial guess (X is zeroed by the library);
  * every column runs its own convergence test and is frozen once it has met it.  its / rnorm / reason: m entries each, host.
- * -ksp_type gmres and -ksp_initial_guess_nonzero (the default of this library: pass -ksp_initial_guess_nonzero 0) are
- * refused.  PCGenEOGetResidualHistory is not extended to blocks.
+ * -ksp_matsolve_type cg|gmres chooses the Krylov method of KSPMatSolve_GenEO alone.  Unset, the method is -ksp_type, which
+ * must then be cg: -ksp_type gmres on its own is refused.  gmres is KSPSolve_GenEO's restarted GMRES (left preconditioning,
+ * classical Gram-Schmidt, Givens residual; -ksp_gmres_restart, -ksp_rtol / atol / divtol / max_it as there) on every column
+ * in lock step, for the non-symmetric modes (RAS, ORAS, the hybrid ones): the columns share the step index and the restart
+ * boundary, each has its own Hessenberg system and test, and a column that met its test is frozen -- its basis columns are
+ * exact zeros from then on.  A step takes all its Gram-Schmidt coefficients from one pass over the basis and one all-reduce
+ * of (k + 1) w values, and the projection with the norms of the remainder from a second pass and an all-reduce of w.  The
+ * basis (restart + 1 slabs at most) is allocated by the first such solve, grown as the steps need it, kept for the next
+ * solve and freed with the set-up: a PC that never runs one pays nothing.
+ * -ksp_initial_guess_nonzero (the default of this library: pass -ksp_initial_guess_nonzero 0) is refused by both
+ * methods.  PCGenEOGetResidualHistory is not extended to blocks.
  * Each returns an error, not a crash, for a set-up without -geneo_block_width, a PC that is not set up, ld < n_owned and
  * m < 1.  The width is read by the set-up: changing the option afterwards has no effect before the next set-up. */
 PetscErrorCode PCMatApply_GenEO(GENEO_PC pc, const double* X_dev, int ldx, double* Y_dev, int ldy, int m);
@@ -211,6 +220,14 @@ PetscErrorCode KSPMatSolve_GenEO(GENEO_PC pc, const double* B_dev, int ldb, doub
  * unavailable).  Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
 int PCGenEOGetBlockInfo(GENEO_PC pc, int* width, long long* slabs, long long* columns, long long* padded,
                         long long* graph_launches);
+/* Block GMRES (-ksp_matsolve_type gmres): *basis_slabs basis slabs held now and *basis_bytes the device bytes of the basis
+ * with its pointer table, coefficients and partial sums (both 0 before the first block GMRES solve of a set-up), and since
+ * the set-up the Gram-Schmidt passes (one for the dots and one for the update of every step, one for the solution update
+ * of every cycle) that went through the fused kernels, *gs_fused, and through their composed forms, *gs_composed
+ * (GeneoSetKernelVariant("block_fused", 0), or a backend without the kernels).  Read-only; any pointer may be NULL.
+ * Returns 0, -1 for a bad handle. */
+int PCGenEOGetBlockKrylovInfo(GENEO_PC pc, int* basis_slabs, double* basis_bytes, long long* gs_fused,
+                              long long* gs_composed);
 /* Since the set-up: how the slabs of the block apply had E^-1 applied to their dimE x w coarse block -- *blocked by the
  * blocked device sweeps on the whole block (a factor made on the device: the launches of one single-vector sweep pair for
  * all w columns), *by_column column by column through the single-vector path (GeneoSetKernelVariant("block_fused", 0), or
