@@ -113,6 +113,7 @@ SYMBOLS = {
     "GeneoFreeInput": (None, [C.POINTER(GeneoInput)]),
     "GeneoTestSparseProduct": (C.c_longlong, [C.c_int, C.POINTER(GeneoCsr), C.POINTER(GeneoCsr), C.c_int, c_int_p, c_int_p, c_dbl_p,
                                C.c_longlong]),
+    "GeneoTestSparseProductReport": (C.c_int, [c_int_p, c_int_p, c_int_p]),
     "GeneoBackendName": (C.c_char_p, []),
     "GeneoSetStream": (C.c_int, [C.c_void_p]),
     "GeneoDecompCreate": (C.c_int, [C.c_int, C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int,

@@ -107,6 +107,15 @@ void csr_free(Csr& a);
 // per-row capacity (the caller falls back to the host product); the returned matrix is then empty.
 Csr  spgemm(const Csr& a, const Csr& b, int ncols_b, bool* ok);
 Csr  transpose(const Csr& a, int ncols, bool* ok);
+// What the calling thread's last spgemm / transpose decided (thread_local: the level-1 hierarchy calls the products from
+// helper threads; host-side stores only, no launch, copy or synchronisation of its own).  A backend without these
+// dispatch paths reports zeros.
+struct SparseProductReport {
+  int group = 0;        // lanes per row of the short-row pass: 0 (none), 8, 16, 32, 64
+  int deferred = 0;     // rows that pass left to the wave-per-row kernels
+  int scan_depth = 0;   // row-pointer scan: 0 host loop, 1 one level of block totals, 2 the totals scanned in more than one block
+};
+SparseProductReport sparse_product_report();
 // P = P0 - w Dinv (A P0) given AP0 = A P0 (in place on its values): P0 = piecewise constant over agg[]
 void smooth_prolongator(Csr& ap0, const int* agg_dev, const double* dinv_dev, double w);
 // finish the SpMV layouts of a matrix whose CSR arrays were just written on the device (spgemm / transpose leave

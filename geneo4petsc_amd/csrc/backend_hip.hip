@@ -1380,6 +1380,8 @@ __global__ __launch_bounds__(256) void k_spgemm_small(int n, const int* __restri
 // two copies of n integers and a serial loop per product -- 10 ms per call at 6.5 M rows, four calls per level).
 // Three-phase scan: 1024-element blocks (LDS), their totals scanned by the same kernel recursively, totals added back.
 constexpr int SCAN_B = 1024;
+static thread_local SparseProductReport t_sp_report;   // what the calling thread's last spgemm / transpose decided (host stores only)
+SparseProductReport sparse_product_report() { return t_sp_report; }
 __global__ __launch_bounds__(256) void k_scan_blocks(int* __restrict__ x, int64_t n, int64_t* __restrict__ totals) {
   __shared__ int64_t part[256];
   const int64_t b0 = (int64_t)blockIdx.x * SCAN_B;
@@ -1448,6 +1450,7 @@ static void device_inclusive_scan64(int64_t* x, int64_t n) {       // block tota
   int64_t* tot = (int64_t*)alloc(sizeof(int64_t) * (size_t)nb);
   hipLaunchKernelGGL(k_scan_blocks64, dim3((unsigned)nb), dim3(256), 0, g_stream, x, n, tot);
   if (nb > 1) {
+    t_sp_report.scan_depth = 2;
     device_inclusive_scan64(tot, nb);
     hipLaunchKernelGGL(k_scan_add64, dim3((unsigned)std::min<int64_t>(nb, 4096)), dim3(256), 0, g_stream, x, n, tot);
   }
@@ -1470,6 +1473,7 @@ static void host_exclusive_scan(int* dcnt_to_ptr, int n, int64_t* total) {   // 
     return;
   }
   int* x = dcnt_to_ptr + 1;
+  t_sp_report.scan_depth = 1;
   const int64_t nb = ((int64_t)n + SCAN_B - 1) / SCAN_B;
   int64_t* tot = (int64_t*)alloc(sizeof(int64_t) * (size_t)nb);
   hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nb), dim3(256), 0, g_stream, x, (int64_t)n, tot);
@@ -1487,6 +1491,7 @@ Csr spgemm(const Csr& a, const Csr& b, int ncols_b, bool* ok) {
   (void)ncols_b;
   Csr c;
   *ok = true;
+  t_sp_report = SparseProductReport();
   c.n = a.n;
   if (a.n == 0) return c;
   int* dflag = (int*)alloc(2 * sizeof(int));          // [0] overflow, [1] rows the group pass left to the wave-per-row kernels
@@ -1500,6 +1505,7 @@ Csr spgemm(const Csr& a, const Csr& b, int ncols_b, bool* ok) {
     else if (na <= 30.0 && est <= 26.0) G = 32;
     else if (na <= 60.0 && est <= 52.0) G = 64;
   }
+  t_sp_report.group = G;
   unsigned char* defer = nullptr;
 #define SPG_SMALL(GG, FILL)                                                                                                  \
   hipLaunchKernelGGL((k_spgemm_small<GG, FILL>), dim3((unsigned)((a.n + 256 / GG - 1) / (256 / GG))), dim3(256), 0, g_stream, \
@@ -1516,6 +1522,7 @@ Csr spgemm(const Csr& a, const Csr& b, int ncols_b, bool* ok) {
     defer = (unsigned char*)alloc((size_t)a.n);
     SPG_SMALL_G(false);
     d2h(hflag, dflag, 2 * sizeof(int));
+    t_sp_report.deferred = hflag[1];
   }
   const bool general = !G || hflag[1] > 0;
   if (general) {
@@ -1604,6 +1611,7 @@ __global__ __launch_bounds__(256) void k_sort_rows(int n, const int* __restrict_
 Csr transpose(const Csr& a, int ncols, bool* ok) {
   Csr t;
   *ok = true;
+  t_sp_report = SparseProductReport();
   t.n = ncols;
   t.nnz = a.nnz;
   t.rowptr = (int*)alloc(sizeof(int) * ((size_t)ncols + 1));

@@ -823,9 +823,9 @@ PetscErrorCode GeneoSpmvOffsetInfo(GeneoSpmv h, int* slices, int* coded) {
 long long GeneoTestSparseProduct(int op, const GeneoCsr* A, const GeneoCsr* B, int ncols, int* rowptr_out, int* col_out,
                                  double* val_out, long long cap) {
   try {
-    bk::Csr a = bk::csr_upload(A->n, A->rowptr, A->col, A->val);
+    bk::Csr a = bk::csr_upload_raw(A->n, A->rowptr, A->col, A->val);     // CSR arrays only: the products read nothing else
     bk::Csr b;
-    if (op == 0) b = bk::csr_upload(B->n, B->rowptr, B->col, B->val);
+    if (op == 0) b = bk::csr_upload_raw(B->n, B->rowptr, B->col, B->val);
     bool ok = true;
     bk::Csr c = (op == 0) ? bk::spgemm(a, b, ncols, &ok) : bk::transpose(a, ncols, &ok);
     long long nnz = ok ? (long long)c.nnz : -1;
@@ -838,6 +838,15 @@ long long GeneoTestSparseProduct(int op, const GeneoCsr* A, const GeneoCsr* B, i
     g_global_err = e.what();
     return -2;
   }
+}
+
+// what the calling thread's last sparse product decided (bk::sparse_product_report); any pointer may be NULL
+int GeneoTestSparseProductReport(int* group, int* deferred, int* scan_depth) {
+  const bk::SparseProductReport r = bk::sparse_product_report();
+  if (group) *group = r.group;
+  if (deferred) *deferred = r.deferred;
+  if (scan_depth) *scan_depth = r.scan_depth;
+  return 0;
 }
 
 // threshold (chunks per subdomain) above which the per-subdomain reductions take their cooperative forms; returns the

@@ -47,6 +47,8 @@ namespace bk {
 __attribute__((weak)) bool coarse_factor(const double*, int, int, double*, double*, int*) { return false; }
 __attribute__((weak)) bool coarse_solve(const double*, const double*, int, int, double*) { return false; }
 __attribute__((weak)) bool coarse_solve_block(const double*, const double*, int, int, double*, int) { return false; }
+// a backend that keeps no record of its sparse products' dispatch links this one: all zeros (backend.h)
+__attribute__((weak)) SparseProductReport sparse_product_report() { return SparseProductReport(); }
 }  // namespace bk
 
 // The step of the Chebyshev local solver composed of backend.h primitives, at any width (w = 1: the vector step of

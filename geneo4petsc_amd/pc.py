@@ -425,6 +425,16 @@ def sparse_product(a, b=None, lib=None):
     return sp.csr_matrix((val[:nnz], col[:nnz], rp), shape=(nrows, ncols if b is not None else a.shape[0]))
 
 
+def sparse_product_report(lib=None):
+    """What the calling thread's last sparse_product decided: the lanes per row of the short-row pass (`group`: 0, 8,
+    16, 32, 64), the rows it left to the wave-per-row kernels (`deferred`) and the depth of the row-pointer scan
+    (`scan_depth`: 0 host loop, 1 one level of block totals, 2 totals scanned in more than one block)."""
+    lib = lib if lib is not None else L.load()
+    g, d, s = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    lib.GeneoTestSparseProductReport(C.byref(g), C.byref(d), C.byref(s))
+    return dict(group=g.value, deferred=d.value, scan_depth=s.value)
+
+
 class Spmv:
     """Stand-alone CSR SpMV / SpMM handle (the roofline kernel of bench.py)."""
 

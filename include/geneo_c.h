@@ -419,6 +419,11 @@ PetscErrorCode GeneoSpmvOffsetInfo(GeneoSpmv h, int* slices, int* coded);
  * row exceeds the kernels' per-row capacity (callers fall back to the host product), -2 on error */
 long long GeneoTestSparseProduct(int op, const GeneoCsr* A, const GeneoCsr* B, int ncols, int* rowptr_out, int* col_out,
                                  double* val_out, long long cap);
+/* what the calling thread's last device sparse product decided (test hook): *group the lanes per row of the short-row
+ * pass (0: none, 8, 16, 32, 64), *deferred the rows that pass left to the wave-per-row kernels, *scan_depth how the row
+ * pointers were scanned (0: host loop, 1: one level of block totals, 2: the totals scanned in more than one block).
+ * A backend without these paths reports zeros.  Any pointer may be NULL.  Returns 0. */
+int GeneoTestSparseProductReport(int* group, int* deferred, int* scan_depth);
 /* per-subdomain tall-skinny kernels on host data (suboff: nsub+1 row offsets):
  *   kind 0: G[s] = S_s^T T_s (p x q)     kind 1: Y_s = S_s C_s (C: nsub x p x q)
  *   kind 2: kind 0 through the two-left-block entry (columns [0, p/2) and [p/2, p) of S passed as separate views)

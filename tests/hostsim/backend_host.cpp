@@ -207,6 +207,7 @@ Csr transpose(const Csr& a, int ncols, bool* ok) {
     for (int k = a.rowptr[i]; k < a.rowptr[i + 1]; ++k) rows[a.col[k]].emplace_back(i, a.val[k]);
   return from_rows(ncols, rows);
 }
+SparseProductReport sparse_product_report() { return SparseProductReport(); }   // no dispatch paths, no capacities
 void smooth_prolongator(Csr& ap0, const int* agg, const double* dinv, double w) {
   for (int i = 0; i < ap0.n; ++i)
     for (int k = ap0.rowptr[i]; k < ap0.rowptr[i + 1]; ++k)

@@ -3,6 +3,8 @@
 
 Hooks: GeneoTestPrimitive (one primitive per call, arguments as tabulated in `_call` below), GeneoTestCgSteps (the
 batched CG sequence with its chunk partials alive across the steps), GeneoTestCsrOp (set-up operations on CSR).
+The cases of the sparse products (GeneoTestSparseProduct, GeneoTestSparseProductReport) live in sparse_product_cases.py
+with their own references and are appended to CASES below.
 
 Techniques common to all cases
   * canaries: every device buffer carries 64 doubles of a sentinel bit pattern in front and behind, padding columns
@@ -33,6 +35,8 @@ import scipy.sparse as sp
 
 from geneo4petsc_amd import _lib as L
 from geneo4petsc_amd.pc import Spmv, _csr_arrays, _csr_struct
+
+import sparse_product_cases as _spc
 
 LD = np.longdouble
 U = 2.0 ** -53
@@ -1051,6 +1055,9 @@ CASES = [case_index, case_blas1, case_seg_dot, case_cg, case_coarse_space, case_
          case_block_elementwise, case_block_colscale_init, case_block_residual, case_block_residual_norms,
          case_gram_block_mul_strided, case_dense_sym_apply, case_chunk_lists_cooperative, case_default_threshold_cooperative,
          case_csr_diag_recip, case_csr_remap_scaled_alias, case_prolongators_post_matrix, case_csr_finish_spmv]
+# the sparse products at every dispatch path and capacity edge (sparse_product_cases.py), found by name like the others
+CASES += _spc.CASES
+globals().update({f.__name__: f for f in _spc.CASES})
 
 # ---------------------------------------------------------------------------------------------- inventory
 # every function declared in namespace bk (csrc/backend.h) -> the cases that call it alone (functions of this module,
@@ -1067,7 +1074,7 @@ INVENTORY = {
     **{f: ("exempt", "event") for f in ("event_create", "event_record", "event_elapsed_ms", "event_destroy")},
     **{f: ("exempt", "graph") for f in ("graph_capture_begin", "graph_capture_end", "graph_launch", "graph_destroy")},
     **{f: ("exempt", "profiling") for f in ("spmv_profile_start", "spmv_profile_stop", "kernel_profile_start",
-                                            "kernel_profile_stop", "kernel_profile_get")},
+                                            "kernel_profile_stop", "kernel_profile_get", "sparse_product_report")},
     **{f: ("exempt", "switch") for f in ("set_spmv_kind", "set_mfma", "set_variant", "set_par_reduce_min",
                                          "get_par_reduce_min")},
     **{f: ("exempt", "predicate") for f in ("csr_has_lp", "csr_fusable", "spmm_dual_available", "lobpcg_update32_available",
@@ -1082,8 +1089,8 @@ INVENTORY = {
     "csr_make_lp": [_K + "test_single_precision_companion"],
     "spmv_lp": [_K + "test_single_precision_companion"],
     "spmv_fused_lp": [_K + "test_single_precision_companion"],
-    "spgemm": [_K + "test_device_sparse_products", "case_csr_finish_spmv"],
-    "transpose": [_K + "test_device_sparse_products"],
+    "spgemm": [_K + "test_device_sparse_products", "case_csr_finish_spmv"] + _spc.SPGEMM_CASES,
+    "transpose": [_K + "test_device_sparse_products"] + _spc.TRANSPOSE_CASES,
     "sell_values_on": [_K + "test_spmm_dual_two_operators_one_pass"],
     "spmm_dual": [_K + "test_spmm_dual_two_operators_one_pass"],
     "spmm_dual_residual": [_K + "test_lean_lobpcg_update_and_residual"],
