@@ -101,6 +101,7 @@ SYMBOLS = {
     "PCGenEOGetBlockInfo": (C.c_int, [C.c_void_p, c_int_p] + [C.POINTER(C.c_longlong)] * 4),
     "PCGenEOGetCoarseBlockCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
     "PCGenEOGetBlockKrylovInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 2),
+    "PCGenEOGetKrylovInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 4),
     "PCGenEOGetInfo": (C.c_int, [C.c_void_p, C.POINTER(GeneoInfo)]),
     "PCGenEOGetEigenvalues": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
     "PCGenEOGetCandidates": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
@@ -171,6 +172,7 @@ SYMBOLS = {
                                    C.c_int, c_dbl_p]),
     "GeneoTestPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
     "GeneoTestBlockPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
+    "GeneoTestKrylovPrimitive": (C.c_int, [C.c_char_p, c_int_p, c_dbl_p, C.POINTER(C.c_void_p)]),
     "PCGenEOGetCoarseInfo": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p]),
     "PCGenEOGetLocalSolverInfo": (C.c_int, [C.c_void_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, C.c_int]),
     "PCGenEOGetLocalSolverTable": (C.c_int, [C.c_void_p, c_dbl_p, C.c_int]),

@@ -16,6 +16,7 @@
 #include "../../include/geneo_c.h"
 #include "amg.h"
 #include "block_dev.h"
+#include "krylov_dev.h"
 #include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "core.h"
@@ -157,6 +158,7 @@ const char* PCGenEOGetOptionsString(PC pc) {
            o.block_width);
   pc->optstr = buf;
   if (!o.ksp_matsolve_type.empty()) pc->optstr += ";ksp_matsolve_type=" + o.ksp_matsolve_type;   // only when set
+  if (!o.ksp_pc_side.empty()) pc->optstr += ";ksp_pc_side=" + o.ksp_pc_side;                     // likewise
   return pc->optstr.c_str();
 }
 const char* PCGenEOGetError(PC pc) { return pc ? pc->err.c_str() : g_global_err.c_str(); }
@@ -208,7 +210,11 @@ const char* usageGenEO_c(void) {
          "  -dls1_amg_strength T / -els2_amg_strength T   aggregation from level 1 on ties |a_ij| >= T 0.5^l sqrt(a_ii a_jj) only\n"
          "  -amg_coarse_size / -amg_smooth_degree / -amg_smooth_ratio / -amg_max_levels\n"
          "  -dls1_amg_smooth_ratio R / -els2_amg_smooth_ratio R   the smoothing interval [rho / R, 1.1 rho] per hierarchy\n"
-         "  -ksp_type cg|gmres -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n"
+         "  -ksp_type cg|gmres|fgmres -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n"
+         "  -ksp_pc_side left|right   (defaults to left) right with -ksp_type gmres: right-preconditioned GMRES, whose convergence\n"
+         "                   test and reported norms are those of the true residual b - A x; -ksp_type fgmres (flexible GMRES,\n"
+         "                   for a preconditioner that changes between applications: -dls1_ksp_type cg at a loose -dls1_ksp_rtol)\n"
+         "                   is always right; not with -ksp_type cg, -geneo_lvl ...,E1 | E2 or KSPMatSolve_GenEO\n"
          "  -ksp_matsolve_type cg|gmres   the Krylov method of KSPMatSolve_GenEO alone (unset: -ksp_type, which must then be cg);\n"
          "                   gmres: restarted GMRES on every column in lock step, for the non-symmetric modes (RAS, ORAS, hybrid)\n\n";
 }
@@ -402,6 +408,12 @@ int PCGenEOGetBlockInfo(PC pc, int* width, long long* slabs, long long* columns,
 int PCGenEOGetBlockKrylovInfo(PC pc, int* basis_slabs, double* basis_bytes, long long* gs_fused, long long* gs_composed) {
   if (!pc || !pc->ctx) return -1;
   pc->ctx->block_krylov_info(basis_slabs, basis_bytes, gs_fused, gs_composed);
+  return 0;
+}
+int PCGenEOGetKrylovInfo(PC pc, int* basis_vectors, double* basis_bytes, long long* gs_fused, long long* gs_composed,
+                         long long* pc_applies, long long* mat_mults) {
+  if (!pc || !pc->ctx) return -1;
+  pc->ctx->krylov_info(basis_vectors, basis_bytes, gs_fused, gs_composed, pc_applies, mat_mults);
   return 0;
 }
 int PCGenEOGetCoarseBlockCounters(PC pc, long long* blocked, long long* by_column, long long* host_blocks) {
@@ -645,6 +657,10 @@ PetscErrorCode GeneoSetKernelVariant(const char* name, int value) {
   }
   if (name && std::string(name) == "block_fused") {    // likewise: the kernels of block_dev.h or their composed forms
     geneo::set_block_fused(value);
+    return 0;
+  }
+  if (name && std::string(name) == "krylov_fused") {   // likewise: the kernels of krylov_dev.h or their composed forms
+    geneo::set_krylov_fused(value);
     return 0;
   }
   return bk::set_variant(name, value) ? 0 : 1;
@@ -1078,6 +1094,37 @@ int GeneoTestBlockPrimitive(const char* name, const int* I, const double* D, voi
     rc = -1;
   }
   if (have_chunks) bk::chunks_free(c);
+  return rc;
+}
+
+// ---- test hook of the Gram-Schmidt primitives of the right-preconditioned GMRES (krylov_dev.h; argument table:
+// tests/krylov_right_util.py) -------------------------------------------------------------------------------------------
+// As GeneoTestBlockPrimitive.  "krylov_fused" 0 runs the composed forms of core.cpp instead.
+int GeneoTestKrylovPrimitive(const char* name, const int* I, const double* D, void* const* P) {
+  (void)D;
+  const std::string k(name ? name : "");
+  auto d = [&](int i) { return (double*)P[i]; };
+  const bool fused = geneo::krylov_fused() != 0;
+  int rc = 0;
+  try {
+    if (k == "vec_gs_group") {                         // the group size of bk::vec_gs_dots, as the return value
+      rc = bk::VEC_GS_GROUP;
+    } else if (k == "vec_dot_nwg") {                   // I(n): the workgroups (partial sums per vector) of a pass over n rows
+      rc = bk::vec_dot_nwg(I[0]);
+    } else if (k == "vec_gs_dots") {                   // I(nb, n)  P(V table, W, H, work)
+      rc = (fused ? bk::vec_gs_dots((const double* const*)P[0], I[0], d(1), I[1], d(2), d(3))
+                  : geneo::vec_gs_dots_composed_once((const double* const*)P[0], I[0], d(1), I[1], d(2))) ? 1 : 0;
+    } else if (k == "vec_gs_update") {                 // I(nb, n)  P(Y, V table, C, norm2 | NULL, work | NULL)
+      rc = (fused ? bk::vec_gs_update(d(0), (const double* const*)P[1], I[0], d(2), I[1], d(3), d(4))
+                  : geneo::vec_gs_update_composed_once(d(0), (const double* const*)P[1], I[0], d(2), I[1], d(3))) ? 1 : 0;
+    } else {
+      rc = -2;
+    }
+    bk::sync();
+  } catch (std::exception& e) {
+    g_global_err = e.what();
+    rc = -1;
+  }
   return rc;
 }
 

@@ -40,6 +40,7 @@
 #include "coarse_dev.h"
 #include "dense.h"
 #include "gmres_col.h"
+#include "krylov_dev.h"
 
 // A backend without the blocked coarse kernels (coarse_dev.h) links these: "not available", nothing touched.  The HIP
 // object's definitions take their place in the product library.
@@ -59,7 +60,9 @@ __attribute__((weak)) SparseProductReport sparse_product_report() { return Spars
 // d .* x and does not read its output.  The scratch (StepWork) belongs to the caller: a PC allocates its own before any
 // graph capture and frees it with the set-up, so nothing is allocated inside a capture and nothing is shared between PCs.
 namespace geneo {
-static std::atomic<int> g_cheb_fused{1}, g_block_fused{1};
+static std::atomic<int> g_cheb_fused{1}, g_block_fused{1}, g_krylov_fused{1};
+void set_krylov_fused(int on) { g_krylov_fused = on ? 1 : 0; }
+int krylov_fused() { return g_krylov_fused.load(); }
 void set_cheb_fused(int on) { g_cheb_fused = on ? 1 : 0; }
 int cheb_fused() { return g_cheb_fused.load(); }
 void set_block_fused(int on) { g_block_fused = on ? 1 : 0; }
@@ -233,6 +236,31 @@ bool block_gs_update_composed_once(double* Y, const double* const* V, int nb, co
   bk::sync();
   return ok;
 }
+// The Gram-Schmidt passes of the right-preconditioned GMRES from bk::dot and bk::axpy, one call per basis vector: what
+// bk::vec_gs_dots and bk::vec_gs_update compute, within rounding (krylov_dev.h).  Vh, Ch: on the HOST.
+bool vec_gs_dots_composed(const double* const* Vh, int nb, const double* W, int n, double* H) {
+  for (int i = 0; i < nb; ++i) bk::dot(Vh[i], W, n, H + i);
+  return true;
+}
+bool vec_gs_update_composed(double* Y, const double* const* Vh, int nb, const double* Ch, int n, double* norm2) {
+  for (int i = 0; i < nb; ++i) bk::axpy(Y, Ch[i], Vh[i], n);
+  if (norm2) bk::dot(Y, Y, n, norm2);
+  return true;
+}
+bool vec_gs_dots_composed_once(const double* const* V, int nb, const double* W, int n, double* H) {
+  const std::vector<const double*> h = table_download(V, nb);
+  const bool ok = vec_gs_dots_composed(h.data(), nb, W, n, H);
+  bk::sync();
+  return ok;
+}
+bool vec_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, double* norm2) {
+  const std::vector<const double*> h = table_download(V, nb);
+  std::vector<double> c(std::max(0, nb));
+  if (nb > 0) bk::d2h(c.data(), C, sizeof(double) * (size_t)nb);
+  const bool ok = vec_gs_update_composed(Y, h.data(), nb, c.data(), n, norm2);
+  bk::sync();
+  return ok;
+}
 bool block_scale_cols_composed_once(double* Out, const double* X, const double* c, int n, int w) {
   if (n <= 0) return true;
   OnceBufs b;
@@ -296,6 +324,15 @@ __attribute__((weak)) bool block_gs_update(double* Y, const double* const* V, in
 __attribute__((weak)) bool block_scale_cols(double* Out, const double* X, const double* c, int n, int w) {
   return geneo::block_scale_cols_composed_once(Out, X, c, n, w);
 }
+// krylov_dev.h: a backend without the kernels links the composed forms (the partial-sum work space is not used)
+__attribute__((weak)) bool vec_gs_dots(const double* const* V, int nb, const double* W, int n, double* H, double*) {
+  return geneo::vec_gs_dots_composed_once(V, nb, W, n, H);
+}
+__attribute__((weak)) bool vec_gs_update(double* Y, const double* const* V, int nb, const double* C, int n, double* norm2,
+                                         double*) {
+  return geneo::vec_gs_update_composed_once(Y, V, nb, C, n, norm2);
+}
+__attribute__((weak)) bool vec_gs_kernels() { return false; }
 }  // namespace bk
 
 namespace geneo {
@@ -335,6 +372,15 @@ static bool to_int(const std::string& s, int& v) {
   } catch (...) {
     return false;
   }
+}
+
+// -ksp_type against -ksp_pc_side: cg is left-preconditioned, fgmres right-preconditioned
+static std::string ksp_side_error(const Options& o) {
+  if (o.ksp_type == "cg" && o.ksp_pc_side == "right")
+    return "GenEO preconditioner: -ksp_pc_side right needs -ksp_type gmres or fgmres (-ksp_type cg is left-preconditioned)";
+  if (o.ksp_type == "fgmres" && o.ksp_pc_side == "left")
+    return "GenEO preconditioner: -ksp_pc_side left is not available with -ksp_type fgmres (flexible GMRES is right-preconditioned)";
+  return "";
 }
 
 std::string parse_option(Options& o, const std::string& key, const std::string& value) {
@@ -477,8 +523,21 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
   if (key == "-els2_amg_smooth_ratio") return dbl(o.els2_amg_smooth_ratio);
   if (key == "-amg_max_levels") return integer(o.amg_max_levels);
   if (key == "-ksp_type") {
-    if (value != "cg" && value != "gmres") return "unsupported -ksp_type " + value;
+    if (value != "cg" && value != "gmres" && value != "fgmres") return "unsupported -ksp_type " + value;
+    Options t = o;                      // an illegal pair is refused here, before it is stored
+    t.ksp_type = value;
+    const std::string e = ksp_side_error(t);
+    if (!e.empty()) return e;
     o.ksp_type = value;
+    return "";
+  }
+  if (key == "-ksp_pc_side") {
+    if (value != "left" && value != "right") return "unsupported -ksp_pc_side " + value + " (left | right)";
+    Options t = o;
+    t.ksp_pc_side = value;
+    const std::string e = ksp_side_error(t);
+    if (!e.empty()) return e;
+    o.ksp_pc_side = value;
     return "";
   }
   if (key == "-ksp_matsolve_type") {
@@ -499,7 +558,7 @@ std::string validate_options(const Options& o) {  // geneo.cpp:2486-2488
   if (o.lvl2 >= 1 && o.tau <= 0.) return "GenEO preconditioner: tau must be > 0.";
   if (o.lvl2 >= 1 && o.tau >= 1.) return "GenEO preconditioner: tau must be < 1.";
   if (o.lvl2 >= 2 && o.gamma <= 1.) return "GenEO preconditioner: gamma must be > 1.";
-  return "";
+  return ksp_side_error(o);
 }
 
 // ------------------------------------------------------------------------------------ helpers
@@ -554,6 +613,7 @@ void PC::free_all() {
   cg_long_len = 0;
   cheb_release();
   block_release();
+  krylov_release();
   delete amg1;
   delete amgN;
   amg1 = amgN = nullptr;
@@ -1516,6 +1576,7 @@ void PC::matmult(const double* X, double* Y, int w, double* WL, double* xe, doub
 
 int PC::matmult(const double* x, double* y) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
+  ++n_mults;
   try {
     matmult(x, y, 1, d_wL, d_xe, d_ye);
   } catch (std::exception& e) {
@@ -2005,6 +2066,7 @@ int PC::apply_q(const double* x, double* y) {
 
 int PC::apply(const double* x, double* y) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
+  ++n_applies;
   try {
     apply_on(vec, x, y);
   } catch (std::exception& e) {
@@ -4508,6 +4570,8 @@ int PC::solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its,
   if (int rc = block_check("KSPMatSolve_GenEO", std::min(ldb, ldx), m, B, X)) return rc;
   if (!its || !rnorm || !reason) return fail("KSPMatSolve_GenEO: its, rnorm and reason need m entries each");
   const std::string& method = opt.ksp_matsolve_type.empty() ? opt.ksp_type : opt.ksp_matsolve_type;
+  if (opt.ksp_pc_side == "right")
+    return fail("KSPMatSolve_GenEO: -ksp_pc_side right has no block form (the block methods are left-preconditioned)");
   if (opt.ksp_matsolve_type.empty() && method != "cg")
     return fail("KSPMatSolve_GenEO: -ksp_type " + opt.ksp_type + " has no block form (the block Krylov method is -ksp_type cg; "
                 "-ksp_matsolve_type gmres selects block GMRES for the block solve alone)");
@@ -4609,15 +4673,198 @@ int PC::solve_gmres(const double* b, double* x, KspResult* res) {
   }
 }
 
+// ---- right-preconditioned and flexible GMRES (-ksp_pc_side right, -ksp_type fgmres) ------------------------------------
+// The memory of solve_gmres_right.  krylov_reserve: the scratch vectors (w; z for the non-flexible method), and the pointer
+// tables, coefficient slots and partial sums of the two Gram-Schmidt passes for `vectors` basis vectors (restart + 1):
+// allocated by the first solve that needs them, replaced when a longer restart asks for more.  krylov_vector: basis vector
+// i, allocated when step i first needs it, its pointer written into slot i of the device table.  Both run between steps
+// (every step ends in a download, so nothing is in flight); a step itself allocates and frees nothing.
+void PC::krylov_reserve(int vectors, bool flexible) {
+  const size_t n = (size_t)std::max(1, n_owned());
+  if (!kr_w) kr_w = (double*)bk::alloc(sizeof(double) * n);
+  if (!flexible && !kr_z) kr_z = (double*)bk::alloc(sizeof(double) * n);
+  if (kr_cap < vectors) {
+    for (void* p : {(void*)kr_Vtab, (void*)kr_Ztab, (void*)kr_h, (void*)kr_c, (void*)kr_n2, (void*)kr_work}) bk::dfree(p);
+    kr_Vtab = (double**)bk::alloc(sizeof(double*) * vectors);
+    kr_Ztab = (double**)bk::alloc(sizeof(double*) * vectors);
+    kr_h = (double*)bk::alloc(sizeof(double) * vectors);
+    kr_c = (double*)bk::alloc(sizeof(double) * vectors);
+    kr_n2 = (double*)bk::alloc(sizeof(double));
+    kr_work = (double*)bk::alloc(sizeof(double) * (size_t)bk::vec_dot_nwg(n_owned()) * vectors);
+    kr_cap = vectors;
+    if (!kr_V.empty()) bk::h2d(kr_Vtab, kr_V.data(), sizeof(double*) * std::min((size_t)vectors, kr_V.size()));
+    if (!kr_Z.empty()) bk::h2d(kr_Ztab, kr_Z.data(), sizeof(double*) * std::min((size_t)vectors, kr_Z.size()));
+  }
+}
+
+double* PC::krylov_vector(std::vector<double*>& basis, double** tab, int i) {
+  while ((int)basis.size() <= i) {
+    basis.push_back((double*)bk::alloc(sizeof(double) * (size_t)std::max(1, n_owned())));
+    const int slot = (int)basis.size() - 1;
+    if (slot < kr_cap) bk::h2d(tab + slot, &basis[slot], sizeof(double*));
+  }
+  return basis[i];
+}
+
+void PC::krylov_release() {
+  for (double* p : kr_V) bk::dfree(p);
+  for (double* p : kr_Z) bk::dfree(p);
+  kr_V.clear();
+  kr_Z.clear();
+  for (void* p : {(void*)kr_w, (void*)kr_z, (void*)kr_Vtab, (void*)kr_Ztab, (void*)kr_h, (void*)kr_c, (void*)kr_n2, (void*)kr_work})
+    bk::dfree(p);
+  kr_w = kr_z = kr_h = kr_c = kr_n2 = kr_work = nullptr;
+  kr_Vtab = kr_Ztab = nullptr;
+  kr_cap = 0;
+  kr_gs_fused = kr_gs_composed = 0;
+  last_applies = last_mults = 0;
+}
+
+void PC::krylov_info(int* basis_vectors, double* basis_bytes, long long* gs_fused, long long* gs_composed,
+                     long long* pc_applies, long long* mat_mults) const {
+  const size_t vecs = kr_V.size() + kr_Z.size() + (kr_w ? 1 : 0) + (kr_z ? 1 : 0);
+  if (basis_vectors) *basis_vectors = (int)vecs;
+  if (basis_bytes)
+    *basis_bytes = (double)(sizeof(double) * vecs * (size_t)std::max(1, n_owned())) +
+                   (kr_cap ? (double)(2 * sizeof(double*) * kr_cap +
+                                      sizeof(double) * (2 * (size_t)kr_cap + 1 + (size_t)bk::vec_dot_nwg(n_owned()) * kr_cap))
+                           : 0.0);
+  if (gs_fused) *gs_fused = kr_gs_fused;
+  if (gs_composed) *gs_composed = kr_gs_composed;
+  if (pc_applies) *pc_applies = last_applies;
+  if (mat_mults) *mat_mults = last_mults;
+}
+
+// Restarted GMRES on A M^-1 (PETSc: -ksp_pc_side right; flexible: -ksp_type fgmres), classical Gram-Schmidt, Givens residual
+// (GmresColumn: the bookkeeping of solve_gmres).  Step k: z = M^-1 v_k (kept as Z_k by the flexible method), w = A z; all
+// h_j = (v_j, w), j <= k, from one pass (bk::vec_gs_dots) and one all-reduce of k + 1 values; w - sum_j h_j v_j with the
+// square of its norm from a second pass (bk::vec_gs_update) and an all-reduce of 1.  A cycle ends with x += sum_j y_j Z_j
+// (flexible: one pass) or x += M^-1 sum_j y_j v_j (one pass and one more application).  The norms are those of the true
+// residual: r_0 = b - A x_0 is recomputed at every restart, the Givens estimate is |b - A x_k| up to rounding -- for the
+// flexible method too, since A Z_k = V_{k+1} H_k holds for any Z -- and with a non-zero guess the test is relative to |b|
+// (KSPConvergedDefault).  Applications of M^-1: its (flexible); its + the cycles that updated x (right).
+int PC::solve_gmres_right(const double* b, double* x, KspResult* res, bool flexible) {
+  const int n = n_owned();
+  const int m = std::max(1, opt.ksp_restart);
+  krylov_reserve(m + 1, flexible);
+  GmresColumn col;
+  col.init(m);
+  ConvTest conv{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol};
+  residual_history.clear();
+  res->its = 0;
+  bool first = true;
+  std::vector<double> hd(m + 1), hc(m + 1);
+  const bool fused = g_krylov_fused.load() != 0 && bk::vec_gs_kernels();
+  auto dots = [&](int nb) {                                 // hd[j] = (v_j, w), j < nb
+    if (fused) {
+      bk::vec_gs_dots(kr_Vtab, nb, kr_w, n, kr_h, kr_work);
+      ++kr_gs_fused;
+    } else {
+      vec_gs_dots_composed(kr_V.data(), nb, kr_w, n, kr_h);
+      ++kr_gs_composed;
+    }
+    allreduce(kr_h, nb);
+    bk::d2h(hd.data(), kr_h, sizeof(double) * nb);
+  };
+  auto update = [&](double* Y, bool zbasis, int nb, bool norm) {   // Y += sum_i hc[i] basis_i; returns the squared norm asked for
+    double* n2 = norm ? kr_n2 : nullptr;
+    if (fused) {
+      bk::h2d(kr_c, hc.data(), sizeof(double) * nb);
+      bk::vec_gs_update(Y, zbasis ? kr_Ztab : kr_Vtab, nb, kr_c, n, n2, kr_work);
+      ++kr_gs_fused;
+    } else {
+      vec_gs_update_composed(Y, zbasis ? kr_Z.data() : kr_V.data(), nb, hc.data(), n, n2);
+      ++kr_gs_composed;
+    }
+    double v = 0.0;
+    if (norm) {
+      allreduce(kr_n2, 1);
+      bk::d2h(&v, kr_n2, sizeof(double));
+    } else {
+      bk::sync();                                            // the next upload may reuse the coefficient slots
+    }
+    return v;
+  };
+  while (true) {
+    double* V0 = krylov_vector(kr_V, kr_Vtab, 0);
+    if (opt.ksp_guess_nonzero || !first) {                   // r = b - A x
+      if (int rc = matmult(x, V0)) return rc;
+      bk::axpby(V0, 1.0, b, -1.0, n);
+    } else {
+      bk::copy(V0, b, n);
+    }
+    double rn = std::sqrt(gdot(V0, V0));
+    if (first) {
+      const double snorm = opt.ksp_guess_nonzero ? std::sqrt(gdot(b, b)) : -1.0;
+      residual_history.push_back(rn);
+      res->rnorm = rn;
+      res->reason = conv(0, rn, snorm);
+      if (res->reason) return 0;
+      first = false;
+    }
+    if (rn == 0.0) { res->reason = 3; return 0; }
+    bk::axpby(V0, 1.0 / rn, V0, 0.0, n);
+    col.start(rn);
+    int k = 0, reason = 0;
+    while (k < m && res->its < opt.ksp_max_it) {
+      double* vk = kr_V[k];
+      double* vn = krylov_vector(kr_V, kr_Vtab, k + 1);
+      double* z = flexible ? krylov_vector(kr_Z, kr_Ztab, k) : kr_z;
+      if (int rc = apply(vk, z)) return rc;
+      if (int rc = matmult(z, kr_w)) return rc;
+      dots(k + 1);
+      for (int j = 0; j <= k; ++j) hc[j] = -hd[j];
+      const double hn = std::sqrt(update(kr_w, false, k + 1, true));
+      rn = col.step(hd.data(), 1, hn);
+      if (col.h[(size_t)k * m + k] == 0.0) {                 // den == 0 in the rotation: the step is dropped
+        col.k = k;
+        reason = -5;                                         // KSP_DIVERGED_BREAKDOWN
+        break;
+      }
+      ++k;
+      res->its++;
+      residual_history.push_back(rn);
+      res->rnorm = rn;
+      reason = conv(res->its, rn, -1.0);
+      if (reason || hn == 0.0) break;                        // hn == 0: happy breakdown, the cycle ends here
+      bk::axpby(vn, 1.0 / hn, kr_w, 0.0, n);
+    }
+    col.solve();
+    for (int j = 0; j < k; ++j) hc[j] = col.y[j];
+    if (k > 0) {
+      if (flexible) {
+        update(x, true, k, false);
+      } else {
+        bk::zero(kr_w, sizeof(double) * (size_t)n);
+        update(kr_w, false, k, false);
+        if (int rc = apply(kr_w, kr_z)) return rc;
+        bk::axpy(x, 1.0, kr_z, n);
+      }
+    }
+    if (reason) { res->reason = reason; return 0; }
+    if (res->its >= opt.ksp_max_it) { res->reason = -3; return 0; }
+  }
+}
+
 int PC::solve(const double* b, double* x, KspResult* res) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
+  const bool right = opt.right_side();
+  if (right && opt.effHybrid)
+    return fail("GenEO preconditioner: -ksp_pc_side right / -ksp_type fgmres is not available with -geneo_lvl ...,E1 | E2 "
+                "(the projected operator and the initial guess Q b of the efficient hybrid are those of left preconditioning)");
   auto t0 = clk::now();
+  const long long a0 = n_applies, m0 = n_mults;
   int rc = 0;
   try {
-    rc = (opt.ksp_type == "cg") ? solve_cg(b, x, res) : solve_gmres(b, x, res);
+    rc = right ? solve_gmres_right(b, x, res, opt.ksp_type == "fgmres")
+               : (opt.ksp_type == "cg") ? solve_cg(b, x, res) : solve_gmres(b, x, res);
   } catch (std::exception& e) {
+    last_applies = n_applies - a0;
+    last_mults = n_mults - m0;
     return fail(e.what());
   }
+  last_applies = n_applies - a0;
+  last_mults = n_mults - m0;
   bk::sync();
   info.solveTime = secs(t0, clk::now());
   return rc;

@@ -107,6 +107,10 @@ struct Options {
   std::string ksp_type = "gmres";
   // -ksp_matsolve_type cg|gmres: the Krylov method of KSPMatSolve_GenEO alone; unset (empty): -ksp_type, which must be cg
   std::string ksp_matsolve_type;
+  // -ksp_pc_side left|right (unset, empty: left).  right with -ksp_type gmres: right-preconditioned GMRES; -ksp_type fgmres
+  // is always right (flexible GMRES: the preconditioner may change from step to step); cg is left only
+  std::string ksp_pc_side;
+  bool right_side() const { return ksp_type == "fgmres" || ksp_pc_side == "right"; }
   double ksp_rtol = 1e-5, ksp_atol = 1e-50, ksp_dtol = 1e5;
   int ksp_max_it = 10000, ksp_restart = 30;
   bool ksp_guess_nonzero = true;   // driver:1348 always sets it
@@ -123,6 +127,9 @@ void set_cheb_fused(int on);
 int cheb_fused();
 void set_block_fused(int on);
 int block_fused();
+// "krylov_fused" 1 (default) the kernels of krylov_dev.h, 0 their composed forms (one bk::dot / bk::axpy per basis vector)
+void set_krylov_fused(int on);
+int krylov_fused();
 struct StepWork {   // scratch of the composed step at width w: one slab, the coefficients spread over the columns, their gather indices
   double *t = nullptr, *ab = nullptr;
   int* idx = nullptr;
@@ -151,6 +158,13 @@ bool block_gs_dots_composed_once(const double* const* V, int nb, const double* W
 bool block_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, int w, double* norm2,
                                    double* work);
 bool block_scale_cols_composed_once(double* Out, const double* X, const double* c, int n, int w);
+// the Gram-Schmidt passes of the right-preconditioned GMRES (krylov_dev.h) from bk::dot and bk::axpy, one call per basis
+// vector (Vh: the vector pointers, Ch: the coefficients, both on the HOST); the _once forms read the pointer table and the
+// coefficients from the device, as bk::vec_gs_dots / bk::vec_gs_update do, and wait
+bool vec_gs_dots_composed(const double* const* Vh, int nb, const double* W, int n, double* H);
+bool vec_gs_update_composed(double* Y, const double* const* Vh, int nb, const double* Ch, int n, double* norm2);
+bool vec_gs_dots_composed_once(const double* const* V, int nb, const double* W, int n, double* H);
+bool vec_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, double* norm2);
 
 struct Info {                 // public counters / timers of geneoContext (hdr/geneo.hpp:96-123)
   int estimDimELoc = 0, realDimELoc = 0, nicolaidesLoc = 0, dimE = 0;
@@ -236,6 +250,12 @@ class PC {
   // (0 before the first block GMRES solve of a set-up), and since the set-up the Gram-Schmidt passes that went through
   // bk::block_gs_dots / bk::block_gs_update and through their composed forms
   void block_krylov_info(int* basis_slabs, double* basis_bytes, long long* gs_fused, long long* gs_composed) const;
+  // right-preconditioned / flexible GMRES (PCGenEOGetKrylovInfo): device vectors held now (basis V, the flexible basis Z
+  // and the scratch vectors) and their bytes with the tables, coefficients and partial sums (0 before the first such solve
+  // of a set-up); since the set-up the Gram-Schmidt passes through bk::vec_gs_dots / bk::vec_gs_update and through their
+  // composed forms; and the preconditioner applications and operator products of the last solve()
+  void krylov_info(int* basis_vectors, double* basis_bytes, long long* gs_fused, long long* gs_composed, long long* pc_applies,
+                   long long* mat_mults) const;
   // since the set-up: slab applications of E^-1 by the blocked block sweeps (bk::coarse_solve_block), column by column
   // through the single-vector path, and by one host round trip of the whole block (PCGenEOGetCoarseBlockCounters)
   void coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const;
@@ -443,6 +463,20 @@ class PC {
   double gdot(const double* x, const double* y);
   int solve_cg(const double* b, double* x, KspResult* res);
   int solve_gmres(const double* b, double* x, KspResult* res);
+  // Right-preconditioned (flexible: Z_k = M^-1 v_k is kept) GMRES.  Its memory -- basis vectors V and Z, scratch vectors,
+  // the device pointer tables, coefficient slots and the partial sums of bk::vec_gs_dots -- is allocated by the first such
+  // solve, grown as the steps need it, kept for the next solve and freed by krylov_release (with the set-up)
+  std::vector<double*> kr_V, kr_Z;
+  double *kr_w = nullptr, *kr_z = nullptr;
+  double **kr_Vtab = nullptr, **kr_Ztab = nullptr;
+  double *kr_h = nullptr, *kr_c = nullptr, *kr_n2 = nullptr, *kr_work = nullptr;
+  int kr_cap = 0;                    // vectors the tables, coefficient slots and partial sums hold
+  long long kr_gs_fused = 0, kr_gs_composed = 0;
+  long long n_applies = 0, n_mults = 0, last_applies = 0, last_mults = 0;   // apply() / matmult() calls: ever, and of the last solve()
+  void krylov_reserve(int vectors, bool flexible);
+  double* krylov_vector(std::vector<double*>& basis, double** tab, int i);
+  void krylov_release();
+  int solve_gmres_right(const double* b, double* x, KspResult* res, bool flexible);
   void free_all();
 };
 

@@ -18,6 +18,7 @@ import numpy as np
 from . import _lib as L
 
 KSP_REASONS = {2: "KSP_CONVERGED_RTOL", 3: "KSP_CONVERGED_ATOL", -3: "KSP_DIVERGED_ITS", -4: "KSP_DIVERGED_DTOL",
+               -5: "KSP_DIVERGED_BREAKDOWN",
                -8: "KSP_DIVERGED_INDEFINITE_MAT", -9: "KSP_DIVERGED_NANORINF", 0: "KSP_CONVERGED_ITERATING"}
 
 
@@ -101,7 +102,7 @@ class GenEOPC:
         out = {}
         for kv in self.lib.PCGenEOGetOptionsString(self.h).decode().split(";"):
             k, _, v = kv.partition("=")
-            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type", "ksp_matsolve_type"):
+            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type", "ksp_matsolve_type", "ksp_pc_side"):
                 out[k] = v
             elif k == "dls1_cheb_safety":
                 out[k] = tuple(float(t) for t in v.split(","))
@@ -294,6 +295,17 @@ class GenEOPC:
         if self.lib.PCGenEOGetBlockKrylovInfo(self.h, C.byref(s), C.byref(b), *[C.byref(x) for x in v]) < 0:
             raise GenEOError("PCGenEOGetBlockKrylovInfo: bad handle")
         return dict(basis_slabs=s.value, basis_bytes=b.value, gs_fused=v[0].value, gs_composed=v[1].value)
+
+    def krylov_info(self):
+        """PCGenEOGetKrylovInfo: device vectors and bytes the right-preconditioned / flexible GMRES (-ksp_pc_side right,
+        -ksp_type fgmres) holds now, since the set-up its Gram-Schmidt passes through the fused kernels and through their
+        composed forms, and the preconditioner applications and operator products of the last solve()."""
+        s, b = C.c_int(0), C.c_double(0.0)
+        v = [C.c_longlong(0) for _ in range(4)]
+        if self.lib.PCGenEOGetKrylovInfo(self.h, C.byref(s), C.byref(b), *[C.byref(x) for x in v]) < 0:
+            raise GenEOError("PCGenEOGetKrylovInfo: bad handle")
+        return dict(basis_vectors=s.value, basis_bytes=b.value, gs_fused=v[0].value, gs_composed=v[1].value,
+                    pc_applies=v[2].value, mat_mults=v[3].value)
 
     def coarse_block_counters(self):
         """PCGenEOGetCoarseBlockCounters since the set-up: slab applications of E^-1 by the blocked sweeps on the whole block,

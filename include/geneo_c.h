@@ -184,6 +184,29 @@ PetscErrorCode PCGenEOSetRHS(GENEO_PC pc, const double* b_dev);
  *      drives PCApply_GenEO instead when PETSc is present) ----------------------------------- */
 PetscErrorCode KSPSolve_GenEO(GENEO_PC pc, const double* b_dev, double* x_dev, int* its, double* rnorm, int* reason);
 int PCGenEOGetResidualHistory(GENEO_PC pc, double* hist, int cap);
+/* -ksp_type cg|gmres|fgmres and -ksp_pc_side left|right (default left) choose the method of KSPSolve_GenEO.  cg and gmres are
+ * left-preconditioned: their convergence test, rnorm and residual history are those of the preconditioned residual.
+ * -ksp_type gmres -ksp_pc_side right is restarted GMRES on A M^-1; -ksp_type fgmres is flexible GMRES, always right, which
+ * keeps z_k = M^-1 v_k of every step and so allows a preconditioner that changes between applications (-dls1_ksp_type cg at
+ * a loose -dls1_ksp_rtol).  Both test, report and record the norm of the TRUE residual b - A x: r_0 is recomputed at every
+ * restart, and with -ksp_initial_guess_nonzero the test is relative to |b|, as KSPConvergedDefault does.  Classical
+ * Gram-Schmidt: a step takes all its coefficients from one pass over the basis and one all-reduce of k + 1 values, and the
+ * projection with the norm of the remainder from a second pass and an all-reduce of one.  reason -5
+ * (KSP_DIVERGED_BREAKDOWN) reports a zero rotation.  The basis (restart + 1 vectors; twice that for fgmres) is allocated by
+ * the first such solve, grown as the steps need it, kept for the next solve and freed with the set-up: a PC that never runs
+ * one pays nothing.
+ * Refused: -ksp_type cg with -ksp_pc_side right, -ksp_type fgmres with -ksp_pc_side left and any other side, when the option
+ * is set; either method with -geneo_lvl ...,E1 | E2, at the solve (the projected operator and the initial guess of the
+ * efficient hybrid are argued for left preconditioning); KSPMatSolve_GenEO with -ksp_pc_side right.  PETSc's own KSP needs
+ * nothing from the PC for -ksp_pc_side right or -ksp_type fgmres: this is the stand-alone driver's counterpart.
+ * PCGenEOGetKrylovInfo: *basis_vectors device vectors these methods hold now (basis, flexible basis and scratch) and
+ * *basis_bytes their bytes with the pointer tables, coefficients and partial sums (both 0 before the first such solve of a
+ * set-up); since the set-up the Gram-Schmidt passes through the fused kernels, *gs_fused, and through their composed forms,
+ * *gs_composed (GeneoSetKernelVariant("krylov_fused", 0), or a backend without the kernels); and the applications of the
+ * preconditioner, *pc_applies, and the operator products, *mat_mults, of the last KSPSolve_GenEO, whatever its method.
+ * Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
+int PCGenEOGetKrylovInfo(GENEO_PC pc, int* basis_vectors, double* basis_bytes, long long* gs_fused, long long* gs_composed,
+                         long long* pc_applies, long long* mat_mults);
 
 /* ---- blocks of right-hand sides (-geneo_block_width 16 | 32; needs -dls1_ksp_type chebyshev) --------------------------
  * The counterparts of pc->ops->matapply, MatMatMult on the MATIS operator and KSPMatSolve.  Blocks are column-major with a
@@ -453,6 +476,10 @@ int GeneoTestPrimitive(const char* name, const int* iarg, const double* darg, vo
 /* The same for the primitives of the block entry points (csrc/block_dev.h); argument table in tests/block_rhs_util.py.
  * Returns the primitive's bool as 0 / 1, -1 on an error, -2 for an unknown name. */
 int GeneoTestBlockPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
+/* The same for the Gram-Schmidt primitives of the right-preconditioned GMRES (csrc/krylov_dev.h): vec_gs_dots,
+ * vec_gs_update, and vec_gs_group / vec_dot_nwg, which return the group size and the partial sums per vector of a pass;
+ * argument table in tests/krylov_right_util.py. */
+int GeneoTestKrylovPrimitive(const char* name, const int* iarg, const double* darg, void* const* parg);
 
 /* ---- the coarse operator E on the device at any dimE (-geneo_coarse_device auto|never|always, -geneo_coarse_block nb) ----
  * Where this PC factored E and how it applies E^-1, after the set-up.  factor_on_device: 1 when the blocked device
