@@ -102,6 +102,7 @@ SYMBOLS = {
     "PCGenEOGetCoarseBlockCounters": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3),
     "PCGenEOGetBlockKrylovInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 2),
     "PCGenEOGetKrylovInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 4),
+    "PCGenEOGetFcgInfo": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p] + [C.POINTER(C.c_longlong)] * 2 + [c_int_p, C.POINTER(C.c_longlong)]),
     "PCGenEOGetInfo": (C.c_int, [C.c_void_p, C.POINTER(GeneoInfo)]),
     "PCGenEOGetEigenvalues": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),
     "PCGenEOGetCandidates": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.c_int]),

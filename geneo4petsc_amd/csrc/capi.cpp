@@ -159,6 +159,9 @@ const char* PCGenEOGetOptionsString(PC pc) {
   pc->optstr = buf;
   if (!o.ksp_matsolve_type.empty()) pc->optstr += ";ksp_matsolve_type=" + o.ksp_matsolve_type;   // only when set
   if (!o.ksp_pc_side.empty()) pc->optstr += ";ksp_pc_side=" + o.ksp_pc_side;                     // likewise
+  if (o.ksp_fcg_mmax_set) pc->optstr += ";ksp_fcg_mmax=" + std::to_string(o.ksp_fcg_mmax);
+  if (!o.ksp_fcg_truncation.empty()) pc->optstr += ";ksp_fcg_truncation_type=" + o.ksp_fcg_truncation;
+  if (!o.ksp_norm_type.empty()) pc->optstr += ";ksp_norm_type=" + o.ksp_norm_type;
   return pc->optstr.c_str();
 }
 const char* PCGenEOGetError(PC pc) { return pc ? pc->err.c_str() : g_global_err.c_str(); }
@@ -210,7 +213,15 @@ const char* usageGenEO_c(void) {
          "  -dls1_amg_strength T / -els2_amg_strength T   aggregation from level 1 on ties |a_ij| >= T 0.5^l sqrt(a_ii a_jj) only\n"
          "  -amg_coarse_size / -amg_smooth_degree / -amg_smooth_ratio / -amg_max_levels\n"
          "  -dls1_amg_smooth_ratio R / -els2_amg_smooth_ratio R   the smoothing interval [rho / R, 1.1 rho] per hierarchy\n"
-         "  -ksp_type cg|gmres|fgmres -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n"
+         "  -ksp_type cg|gmres|fgmres|fcg -ksp_rtol -ksp_atol -ksp_max_it -ksp_gmres_restart\n"
+         "  -ksp_type fcg    flexible CG (left-preconditioned, short recurrences, the norms of cg) for the symmetric modes with a\n"
+         "                   preconditioner that changes between applications (-dls1_ksp_type cg at a loose -dls1_ksp_rtol);\n"
+         "                   not with -ksp_pc_side right or KSPMatSolve_GenEO\n"
+         "  -ksp_fcg_mmax M  (defaults to 30, M >= 1) directions a new direction is made conjugate to, at most\n"
+         "  -ksp_fcg_truncation_type notay|standard   (defaults to notay) the window grows from 1 to M and starts again, or is\n"
+         "                   always the M most recent directions\n"
+         "  -ksp_norm_type preconditioned|unpreconditioned   (defaults to preconditioned) unpreconditioned, with -ksp_type fcg\n"
+         "                   only: the convergence test and the reported norms are those of the true residual b - A x\n"
          "  -ksp_pc_side left|right   (defaults to left) right with -ksp_type gmres: right-preconditioned GMRES, whose convergence\n"
          "                   test and reported norms are those of the true residual b - A x; -ksp_type fgmres (flexible GMRES,\n"
          "                   for a preconditioner that changes between applications: -dls1_ksp_type cg at a loose -dls1_ksp_rtol)\n"
@@ -414,6 +425,12 @@ int PCGenEOGetKrylovInfo(PC pc, int* basis_vectors, double* basis_bytes, long lo
                          long long* pc_applies, long long* mat_mults) {
   if (!pc || !pc->ctx) return -1;
   pc->ctx->krylov_info(basis_vectors, basis_bytes, gs_fused, gs_composed, pc_applies, mat_mults);
+  return 0;
+}
+int PCGenEOGetFcgInfo(PC pc, int* directions, double* bytes, long long* steps_fused, long long* steps_composed, int* max_window,
+                      long long* downloads) {
+  if (!pc || !pc->ctx) return -1;
+  pc->ctx->fcg_info(directions, bytes, steps_fused, steps_composed, max_window, downloads);
   return 0;
 }
 int PCGenEOGetCoarseBlockCounters(PC pc, long long* blocked, long long* by_column, long long* host_blocks) {
@@ -1117,6 +1134,9 @@ int GeneoTestKrylovPrimitive(const char* name, const int* I, const double* D, vo
     } else if (k == "vec_gs_update") {                 // I(nb, n)  P(Y, V table, C, norm2 | NULL, work | NULL)
       rc = (fused ? bk::vec_gs_update(d(0), (const double* const*)P[1], I[0], d(2), I[1], d(3), d(4))
                   : geneo::vec_gs_update_composed_once(d(0), (const double* const*)P[1], I[0], d(2), I[1], d(3))) ? 1 : 0;
+    } else if (k == "vec_fcg_step") {                  // I(n)  P(x, r, p, w, S, norm2 | NULL, work | NULL)
+      rc = (fused ? bk::vec_fcg_step(d(0), d(1), d(2), d(3), d(4), I[0], d(5), d(6))
+                  : geneo::vec_fcg_step_composed(d(0), d(1), d(2), d(3), d(4), I[0], d(5))) ? 1 : 0;
     } else {
       rc = -2;
     }

@@ -39,6 +39,7 @@
 #include "cheb_dev.h"
 #include "coarse_dev.h"
 #include "dense.h"
+#include "fcg_window.h"
 #include "gmres_col.h"
 #include "krylov_dev.h"
 
@@ -261,6 +262,19 @@ bool vec_gs_update_composed_once(double* Y, const double* const* V, int nb, cons
   bk::sync();
   return ok;
 }
+// The step of the flexible CG from bk::axpy and bk::dot: what bk::vec_fcg_step computes, within rounding (krylov_dev.h).
+// alpha is formed on the HOST from a download of S; eta not positive (or NaN): x and r stay as they are.
+bool vec_fcg_step_composed(double* x, double* r, const double* p, const double* w, const double* S, int n, double* norm2) {
+  double s[2] = {0.0, 0.0};
+  bk::d2h(s, S, sizeof(s));
+  if (s[0] > 0.0) {
+    const double a = s[1] / s[0];
+    bk::axpy(x, a, p, n);
+    bk::axpy(r, -a, w, n);
+  }
+  if (norm2) bk::dot(r, r, n, norm2);
+  return true;
+}
 bool block_scale_cols_composed_once(double* Out, const double* X, const double* c, int n, int w) {
   if (n <= 0) return true;
   OnceBufs b;
@@ -332,6 +346,12 @@ __attribute__((weak)) bool vec_gs_update(double* Y, const double* const* V, int 
                                          double*) {
   return geneo::vec_gs_update_composed_once(Y, V, nb, C, n, norm2);
 }
+__attribute__((weak)) bool vec_fcg_step(double* x, double* r, const double* p, const double* w, const double* S, int n,
+                                        double* norm2, double*) {
+  const bool ok = geneo::vec_fcg_step_composed(x, r, p, w, S, n, norm2);
+  bk::sync();
+  return ok;
+}
 __attribute__((weak)) bool vec_gs_kernels() { return false; }
 }  // namespace bk
 
@@ -378,6 +398,8 @@ static bool to_int(const std::string& s, int& v) {
 static std::string ksp_side_error(const Options& o) {
   if (o.ksp_type == "cg" && o.ksp_pc_side == "right")
     return "GenEO preconditioner: -ksp_pc_side right needs -ksp_type gmres or fgmres (-ksp_type cg is left-preconditioned)";
+  if (o.ksp_type == "fcg" && o.ksp_pc_side == "right")
+    return "GenEO preconditioner: -ksp_pc_side right needs -ksp_type gmres or fgmres (-ksp_type fcg is left-preconditioned)";
   if (o.ksp_type == "fgmres" && o.ksp_pc_side == "left")
     return "GenEO preconditioner: -ksp_pc_side left is not available with -ksp_type fgmres (flexible GMRES is right-preconditioned)";
   return "";
@@ -523,7 +545,7 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
   if (key == "-els2_amg_smooth_ratio") return dbl(o.els2_amg_smooth_ratio);
   if (key == "-amg_max_levels") return integer(o.amg_max_levels);
   if (key == "-ksp_type") {
-    if (value != "cg" && value != "gmres" && value != "fgmres") return "unsupported -ksp_type " + value;
+    if (value != "cg" && value != "gmres" && value != "fgmres" && value != "fcg") return "unsupported -ksp_type " + value;
     Options t = o;                      // an illegal pair is refused here, before it is stored
     t.ksp_type = value;
     const std::string e = ksp_side_error(t);
@@ -538,6 +560,25 @@ std::string parse_option(Options& o, const std::string& key, const std::string& 
     const std::string e = ksp_side_error(t);
     if (!e.empty()) return e;
     o.ksp_pc_side = value;
+    return "";
+  }
+  if (key == "-ksp_fcg_mmax") {
+    int v;
+    if (!to_int(value, v) || v < 1 || std::to_string(v) != value)      // "3.5", "2x": not an integer either
+      return "invalid option -ksp_fcg_mmax, " + value + " is not an integer >= 1";
+    o.ksp_fcg_mmax = v;
+    o.ksp_fcg_mmax_set = true;
+    return "";
+  }
+  if (key == "-ksp_fcg_truncation_type") {
+    if (value != "notay" && value != "standard") return "unsupported -ksp_fcg_truncation_type " + value + " (notay | standard)";
+    o.ksp_fcg_truncation = value;
+    return "";
+  }
+  if (key == "-ksp_norm_type") {
+    if (value != "preconditioned" && value != "unpreconditioned")
+      return "unsupported -ksp_norm_type " + value + " (preconditioned | unpreconditioned)";
+    o.ksp_norm_type = value;
     return "";
   }
   if (key == "-ksp_matsolve_type") {
@@ -614,6 +655,7 @@ void PC::free_all() {
   cheb_release();
   block_release();
   krylov_release();
+  fcg_release();
   delete amg1;
   delete amgN;
   amg1 = amgN = nullptr;
@@ -4575,6 +4617,9 @@ int PC::solve_mat(const double* B, int ldb, double* X, int ldx, int m, int* its,
   if (opt.ksp_matsolve_type.empty() && method != "cg")
     return fail("KSPMatSolve_GenEO: -ksp_type " + opt.ksp_type + " has no block form (the block Krylov method is -ksp_type cg; "
                 "-ksp_matsolve_type gmres selects block GMRES for the block solve alone)");
+  if (opt.ksp_norm_type == "unpreconditioned")
+    return fail("KSPMatSolve_GenEO: -ksp_norm_type unpreconditioned needs -ksp_type fcg, which has no block form (the block "
+                "methods test the preconditioned residual)");
   if (opt.ksp_guess_nonzero)
     return fail("KSPMatSolve_GenEO: -ksp_initial_guess_nonzero is not supported (the block solve starts from zero: "
                 "-ksp_initial_guess_nonzero 0)");
@@ -4846,8 +4891,234 @@ int PC::solve_gmres_right(const double* b, double* x, KspResult* res, bool flexi
   }
 }
 
+// ---- flexible CG (-ksp_type fcg) ----------------------------------------------------------------------------------------
+// The memory of solve_fcg.  fcg_reserve: the residual, the three pointer tables, the scalars, the coefficient slots and the
+// partial sums for a ring of `slots` directions; everything is released first when the number of slots changes.
+// fcg_vector: the direction (or product) of a ring slot, allocated when a step first needs it, its pointer written into the
+// tables.  Both run where no kernel that reads the entries they write is in flight: a table entry is written before the
+// first launch that names it.
+void PC::fcg_reserve(int slots) {
+  if (fc_slots == slots) return;
+  const long long fused = fc_steps_fused, composed = fc_steps_composed;
+  fcg_release();
+  fc_steps_fused = fused;
+  fc_steps_composed = composed;
+  const size_t n = (size_t)std::max(1, n_owned());
+  fc_slots = slots;
+  fc_P.assign((size_t)slots, nullptr);
+  fc_W.assign((size_t)slots, nullptr);
+  fc_Ph.assign((size_t)2 * slots, nullptr);
+  fc_Wh.assign((size_t)2 * slots, nullptr);
+  fc_r = (double*)bk::alloc(sizeof(double) * n);
+  fc_Ptab = (double**)bk::alloc(sizeof(double*) * 2 * slots);
+  fc_Wtab = (double**)bk::alloc(sizeof(double*) * 2 * slots);
+  fc_Btab = (double**)bk::alloc(sizeof(double*) * 2 * slots);
+  fc_s = (double*)bk::alloc(sizeof(double) * (3 + (size_t)slots));
+  fc_c = (double*)bk::alloc(sizeof(double) * slots);
+  fc_work = (double*)bk::alloc(sizeof(double) * (size_t)bk::vec_dot_nwg(n_owned()) * std::max(2, slots));
+  std::vector<double*> pairs((size_t)2 * slots, nullptr);
+  for (int s = 0; s < slots; ++s) pairs[(size_t)2 * s + 1] = fc_r;       // {w of the slot (fcg_vector), r}
+  bk::h2d(fc_Btab, pairs.data(), sizeof(double*) * pairs.size());
+}
+
+double* PC::fcg_vector(bool product, int slot) {
+  std::vector<double*>& ring = product ? fc_W : fc_P;
+  if (!ring[slot]) {
+    double* v = (double*)bk::alloc(sizeof(double) * (size_t)std::max(1, n_owned()));
+    ring[slot] = v;
+    std::vector<double*>& host = product ? fc_Wh : fc_Ph;
+    double** tab = product ? fc_Wtab : fc_Ptab;
+    host[slot] = host[(size_t)slot + fc_slots] = v;
+    bk::h2d(tab + slot, &v, sizeof(double*));
+    bk::h2d(tab + slot + fc_slots, &v, sizeof(double*));
+    if (product) bk::h2d(fc_Btab + 2 * slot, &v, sizeof(double*));
+  }
+  return ring[slot];
+}
+
+void PC::fcg_release() {
+  for (double* p : fc_P) bk::dfree(p);
+  for (double* p : fc_W) bk::dfree(p);
+  fc_P.clear();
+  fc_W.clear();
+  fc_Ph.clear();
+  fc_Wh.clear();
+  for (void* p : {(void*)fc_r, (void*)fc_Ptab, (void*)fc_Wtab, (void*)fc_Btab, (void*)fc_s, (void*)fc_c, (void*)fc_work}) bk::dfree(p);
+  fc_r = fc_s = fc_c = fc_work = nullptr;
+  fc_Ptab = fc_Wtab = fc_Btab = nullptr;
+  fc_slots = fc_max_window = 0;
+  fc_steps_fused = fc_steps_composed = fc_downloads = 0;
+}
+
+void PC::fcg_info(int* directions, double* bytes, long long* steps_fused, long long* steps_composed, int* max_window,
+                  long long* downloads) const {
+  size_t pairs = 0, vecs = fc_r ? 1 : 0;
+  for (double* p : fc_W) pairs += p ? 1 : 0;
+  for (double* p : fc_P) vecs += p ? 1 : 0;
+  vecs += pairs;
+  if (directions) *directions = (int)pairs;
+  if (bytes)
+    *bytes = (double)(sizeof(double) * vecs * (size_t)std::max(1, n_owned())) +
+             (fc_slots ? (double)(3 * sizeof(double*) * 2 * (size_t)fc_slots +
+                                  sizeof(double) * (3 + 2 * (size_t)fc_slots +
+                                                    (size_t)bk::vec_dot_nwg(n_owned()) * std::max(2, fc_slots)))
+                       : 0.0);
+  if (steps_fused) *steps_fused = fc_steps_fused;
+  if (steps_composed) *steps_composed = fc_steps_composed;
+  if (max_window) *max_window = fc_max_window;
+  if (downloads) *downloads = fc_downloads;
+}
+
+// Flexible CG (Notay 2000; PETSc KSPFCG), left-preconditioned, for a preconditioner that changes between applications.
+// Iteration i: z = M^-1 r, written into the ring slot of the new direction; h_k = (w_k, z) for the m_i directions of the
+// window (fcg_window.h) and (z, z) from bk::vec_gs_dots, one all-reduce, one download -- which also brings eta_{i-1}, left
+// on the device by the step before; the test on |z| (ConvTest, as solve_cg); p_i = z - sum_k (h_k / eta_k) p_k in place
+// (bk::vec_gs_update); w_i = A p_i; [eta_i, pi_i] = [(w_i, p_i), (r, p_i)] from one pass and one all-reduce, not
+// downloaded; bk::vec_fcg_step forms alpha = pi_i / eta_i on the device and updates x and r.  One host round trip per
+// iteration where solve_cg makes three.  An eta that is not positive leaves x and r untouched and is seen with the next
+// download: KSP_DIVERGED_INDEFINITE_MAT with the its of the iteration that made it.
+// -ksp_norm_type unpreconditioned: the step also returns |r|^2; the test follows the step, on |r| = |b - A x| (relative to
+// |b| with a guess, as solve_gmres_right), and no application follows the last step.
+// The window's dot products and (z, z) are two launches of the same kernel into one buffer: the tables are written once,
+// and the entry behind a window names the product of the slot that z occupies, not z.
+int PC::solve_fcg(const double* b, double* x, KspResult* res) {
+  const int n = n_owned();
+  const bool unprec = opt.ksp_norm_type == "unpreconditioned";
+  FcgWindow win;
+  win.init(opt.ksp_fcg_mmax, opt.ksp_fcg_truncation != "standard");
+  fcg_reserve(win.slots);
+  const int S = win.slots, nwg = bk::vec_dot_nwg(n);
+  const bool fused = g_krylov_fused.load() != 0 && bk::vec_gs_kernels();
+  ConvTest conv{opt.ksp_rtol, opt.ksp_atol, opt.ksp_dtol};
+  residual_history.clear();
+  fc_max_window = 0;
+  fc_downloads = 0;
+  res->its = 0;
+  double *r = fc_r, *sn2 = fc_s, *sS = fc_s + 1, *sh = fc_s + 3;
+  bk::zero(fc_s, sizeof(double) * (3 + (size_t)S));
+  std::vector<double> hd(3 + (size_t)S), hc((size_t)S);
+  auto norm_of = [&](const double* v) {                            // a gdot is a download of its own
+    ++fc_downloads;
+    return std::sqrt(gdot(v, v));
+  };
+  auto download = [&](const double* src, int cnt) {
+    bk::d2h(hd.data(), src, sizeof(double) * (size_t)cnt);
+    ++fc_downloads;
+  };
+  // sh[j] = (w_k, z), k = first(i) + j, j < m, and with zz sh[m] = (z, z); all-reduced
+  auto window_dots = [&](int i, int m, bool zz) {
+    const int slot = win.slot(i), off = win.offset(i);
+    const double* z = fc_P[slot];
+    if (fused) {
+      if (m > 0) bk::vec_gs_dots(fc_Wtab + off, m, z, n, sh, fc_work);
+      if (zz) bk::vec_gs_dots(fc_Ptab + slot, 1, z, n, sh + m, fc_work + (size_t)nwg * m);
+    } else {
+      if (m > 0) vec_gs_dots_composed(fc_Wh.data() + off, m, z, n, sh);
+      if (zz) bk::dot(z, z, n, sh + m);
+    }
+    allreduce(sh, m + (zz ? 1 : 0));
+  };
+  // p_i from z and the window (h: its m dot products), w_i = A p_i, [eta_i, pi_i] and the step
+  auto advance = [&](int i, int m, const double* h, bool norm) -> int {
+    const int slot = win.slot(i), off = win.offset(i);
+    double* p = fc_P[slot];
+    fc_max_window = std::max(fc_max_window, m);
+    if (m > 0) {
+      for (int j = 0; j < m; ++j) hc[j] = -h[j] / win.eta_of(win.first(i) + j);
+      if (fused) {
+        bk::h2d(fc_c, hc.data(), sizeof(double) * (size_t)m);
+        bk::vec_gs_update(p, fc_Ptab + off, m, fc_c, n, nullptr, fc_work);
+      } else {
+        vec_gs_update_composed(p, fc_Ph.data() + off, m, hc.data(), n, nullptr);
+      }
+    }
+    double* w = fcg_vector(true, slot);
+    if (int rc = matmult(p, w)) return rc;
+    if (fused) {
+      bk::vec_gs_dots(fc_Btab + 2 * slot, 2, p, n, sS, fc_work);
+    } else {
+      bk::dot(w, p, n, sS);
+      bk::dot(r, p, n, sS + 1);
+    }
+    allreduce(sS, 2);
+    if (fused) {
+      bk::vec_fcg_step(x, r, p, w, sS, n, norm ? sn2 : nullptr, fc_work);
+      ++fc_steps_fused;
+    } else {
+      vec_fcg_step_composed(x, r, p, w, sS, n, norm ? sn2 : nullptr);
+      ++fc_steps_composed;
+      ++fc_downloads;                                              // of S, by the composed step
+    }
+    return 0;
+  };
+
+  if (opt.ksp_guess_nonzero) {
+    if (int rc = matmult(x, r)) return rc;
+    bk::axpby(r, 1.0, b, -1.0, n);  // r = b - A x
+  } else {
+    bk::copy(r, b, n);
+  }
+  if (unprec) {
+    double rn = norm_of(r);
+    const double snorm = opt.ksp_guess_nonzero ? norm_of(b) : -1.0;
+    residual_history.push_back(rn);
+    res->rnorm = rn;
+    res->reason = conv(0, rn, snorm);
+    if (res->reason) return 0;
+    for (int i = 0; i < opt.ksp_max_it; ++i) {
+      res->its = i + 1;
+      const int m = win.size(i);
+      if (int rc = apply(r, fcg_vector(false, win.slot(i)))) return rc;
+      if (m > 0) {
+        window_dots(i, m, false);
+        download(sh, m);
+      }
+      if (int rc = advance(i, m, hd.data(), true)) return rc;
+      allreduce(sn2, 1);
+      download(sn2, 3);                                            // |r|^2, eta_i, pi_i
+      win.eta_of(i) = hd[1];
+      if (!(hd[1] > 0.0)) { res->reason = -8; return 0; }          // KSP_DIVERGED_INDEFINITE_MAT: the step changed nothing
+      rn = std::sqrt(hd[0]);
+      residual_history.push_back(rn);
+      res->rnorm = rn;
+      res->reason = conv(i + 1, rn, -1.0);
+      if (res->reason) return 0;
+    }
+    res->reason = -3;
+    return 0;
+  }
+  for (int i = 0;; ++i) {
+    const int m = win.size(i);
+    if (int rc = apply(r, fcg_vector(false, win.slot(i)))) return rc;
+    double snorm = -1.0;
+    if (i == 0 && opt.ksp_guess_nonzero) {
+      DeviceVectors tmp;
+      double* t = tmp.get(n);
+      if (int rc = apply(b, t)) return rc;
+      snorm = norm_of(t);
+    }
+    window_dots(i, m, true);
+    download(sS, 2 + m + 1);                                       // eta_{i-1}, pi_{i-1}, h_0 .. h_{m-1}, (z, z)
+    if (i > 0) {
+      win.eta_of(i - 1) = hd[0];
+      if (!(hd[0] > 0.0)) { res->reason = -8; return 0; }          // KSP_DIVERGED_INDEFINITE_MAT, its of that iteration
+    }
+    const double dp = std::sqrt(hd[2 + (size_t)m]);
+    residual_history.push_back(dp);
+    res->rnorm = dp;
+    res->reason = conv(i, dp, snorm);
+    if (res->reason) return 0;
+    if (i >= opt.ksp_max_it) { res->reason = -3; return 0; }
+    res->its = i + 1;
+    if (int rc = advance(i, m, hd.data() + 2, false)) return rc;
+  }
+}
+
 int PC::solve(const double* b, double* x, KspResult* res) {
   if (!is_setup) return fail("GenEO preconditioner is not set up");
+  if (opt.ksp_norm_type == "unpreconditioned" && opt.ksp_type != "fcg")
+    return fail("GenEO preconditioner: -ksp_norm_type unpreconditioned needs -ksp_type fcg (-ksp_type " + opt.ksp_type +
+                " has one norm: cg and left gmres test the preconditioned residual, right gmres and fgmres the true one)");
   const bool right = opt.right_side();
   if (right && opt.effHybrid)
     return fail("GenEO preconditioner: -ksp_pc_side right / -ksp_type fgmres is not available with -geneo_lvl ...,E1 | E2 "
@@ -4857,7 +5128,8 @@ int PC::solve(const double* b, double* x, KspResult* res) {
   int rc = 0;
   try {
     rc = right ? solve_gmres_right(b, x, res, opt.ksp_type == "fgmres")
-               : (opt.ksp_type == "cg") ? solve_cg(b, x, res) : solve_gmres(b, x, res);
+               : (opt.ksp_type == "cg") ? solve_cg(b, x, res)
+               : (opt.ksp_type == "fcg") ? solve_fcg(b, x, res) : solve_gmres(b, x, res);
   } catch (std::exception& e) {
     last_applies = n_applies - a0;
     last_mults = n_mults - m0;

@@ -111,6 +111,13 @@ struct Options {
   // is always right (flexible GMRES: the preconditioner may change from step to step); cg is left only
   std::string ksp_pc_side;
   bool right_side() const { return ksp_type == "fgmres" || ksp_pc_side == "right"; }
+  // -ksp_type fcg (flexible CG, left-preconditioned): -ksp_fcg_mmax m >= 1 directions a new one is made conjugate to,
+  // -ksp_fcg_truncation_type notay|standard (csrc/fcg_window.h), -ksp_norm_type preconditioned|unpreconditioned (unset,
+  // empty: preconditioned; unpreconditioned is fcg's alone: the test is on |b - A x|, which its step returns)
+  int ksp_fcg_mmax = 30;
+  bool ksp_fcg_mmax_set = false;
+  std::string ksp_fcg_truncation;    // unset (empty): notay
+  std::string ksp_norm_type;
   double ksp_rtol = 1e-5, ksp_atol = 1e-50, ksp_dtol = 1e5;
   int ksp_max_it = 10000, ksp_restart = 30;
   bool ksp_guess_nonzero = true;   // driver:1348 always sets it
@@ -165,6 +172,8 @@ bool vec_gs_dots_composed(const double* const* Vh, int nb, const double* W, int 
 bool vec_gs_update_composed(double* Y, const double* const* Vh, int nb, const double* Ch, int n, double* norm2);
 bool vec_gs_dots_composed_once(const double* const* V, int nb, const double* W, int n, double* H);
 bool vec_gs_update_composed_once(double* Y, const double* const* V, int nb, const double* C, int n, double* norm2);
+// bk::vec_fcg_step from backend.h primitives: S ([eta, pi], on the device) is downloaded, then bk::axpy, bk::axpy, bk::dot
+bool vec_fcg_step_composed(double* x, double* r, const double* p, const double* w, const double* S, int n, double* norm2);
 
 struct Info {                 // public counters / timers of geneoContext (hdr/geneo.hpp:96-123)
   int estimDimELoc = 0, realDimELoc = 0, nicolaidesLoc = 0, dimE = 0;
@@ -259,6 +268,11 @@ class PC {
   // since the set-up: slab applications of E^-1 by the blocked block sweeps (bk::coarse_solve_block), column by column
   // through the single-vector path, and by one host round trip of the whole block (PCGenEOGetCoarseBlockCounters)
   void coarse_block_counters(long long* blocked, long long* by_column, long long* host_blocks) const;
+  // flexible CG (PCGenEOGetFcgInfo): direction / product pairs held now and the device bytes of everything the method
+  // holds (0 before the first fcg solve of a set-up); since the set-up the steps through bk::vec_fcg_step and through its
+  // composed form; of the last fcg solve the largest window and the downloads (device-to-host copies the host waited for)
+  void fcg_info(int* directions, double* bytes, long long* steps_fused, long long* steps_composed, int* max_window,
+                long long* downloads) const;
   int n_owned() const { return (int)owned.size(); }
   int cheb_steps_per_solve() const { return cheb_K; }
   void cheb_counters(long long* solves, long long* graph_launches, long long* fused_residuals) const {
@@ -477,6 +491,21 @@ class PC {
   double* krylov_vector(std::vector<double*>& basis, double** tab, int i);
   void krylov_release();
   int solve_gmres_right(const double* b, double* x, KspResult* res, bool flexible);
+  // Flexible CG.  Ring slot s (fcg_window.h) holds direction fc_P[s] and its product fc_W[s], each allocated when a step
+  // first needs it.  fc_Ptab / fc_Wtab: device tables that name every slot twice (a window is contiguous in them);
+  // fc_Btab: per slot the pair {w, r} of the step's two dot products; fc_s: [|r|^2, eta, pi, h_0 .. h_slots-1] so that one
+  // download brings the scalars a test needs.  All of it is allocated by the first fcg solve (again when -ksp_fcg_mmax
+  // changes the number of slots) and freed by fcg_release (with the set-up).
+  std::vector<double*> fc_P, fc_W, fc_Ph, fc_Wh;   // fc_Ph / fc_Wh: host copies of the two doubled tables (composed forms)
+  double* fc_r = nullptr;
+  double **fc_Ptab = nullptr, **fc_Wtab = nullptr, **fc_Btab = nullptr;
+  double *fc_s = nullptr, *fc_c = nullptr, *fc_work = nullptr;
+  int fc_slots = 0, fc_max_window = 0;
+  long long fc_steps_fused = 0, fc_steps_composed = 0, fc_downloads = 0;
+  void fcg_reserve(int slots);
+  double* fcg_vector(bool product, int slot);
+  void fcg_release();
+  int solve_fcg(const double* b, double* x, KspResult* res);
   void free_all();
 };
 

@@ -47,7 +47,16 @@ bool vec_gs_dots(const double* const* V, int nb, const double* W, int n, double*
 // (vec_dot_nwg(n) doubles) is needed, and written, with norm2 only.
 bool vec_gs_update(double* Y, const double* const* V, int nb, const double* C, int n, double* norm2, double* work);
 
-// true where the two functions above are the kernels (the HIP object), false where they are core.cpp's composed forms: the
+// The step of the flexible CG (-ksp_type fcg) with its coefficient on the device.  S: two doubles ON THE DEVICE, [eta, pi]
+// = [(A p, p), (r, p)].  alpha = pi / eta (correctly rounded); x[r] = fl(x[r] + fl(alpha p[r])), r[r] = fl(r[r] -
+// fl(alpha w[r])) in one pass, with the row ranges, lane map and load paths of vec_gs_update.  If eta is not positive (zero,
+// negative, NaN) nothing is written to x or r.  norm2 (one double, may be null): sum_r r'[r]^2 of r as the call leaves it,
+// with the bits vec_gs_dots(&r', 1, r') gives; work (vec_dot_nwg(n) doubles) is needed, and written, with norm2 only.
+// Bytes, from the definitions: fused 6 x 8 n, one launch (two with norm2), no download; composed (core.cpp: download S,
+// bk::axpy, bk::axpy, bk::dot) 8 x 8 n, three launches and a download.
+bool vec_fcg_step(double* x, double* r, const double* p, const double* w, const double* S, int n, double* norm2, double* work);
+
+// true where the functions above are the kernels (the HIP object), false where they are core.cpp's composed forms: the
 // driver then runs those on its host copies of the pointer table and the coefficients, and counts its passes as composed
 bool vec_gs_kernels();
 

@@ -13,6 +13,10 @@
 //                              k_vec_dots1 owns, so that the squares of the result are summed in its order (NORM): the
 //                              partials of vec_gs_dots(&y', 1, y').  The coefficients of a launch (at most VEC_GS_NBMAX
 //                              vectors; the wrapper splits longer lists) sit in LDS.
+//   k_vec_fcg_step             the step of the flexible CG on the rows and lanes of k_vec_update: every workgroup reads
+//                              [eta, pi] and forms alpha = pi / eta; x <- fl(x + fl(alpha p)), r <- fl(r - fl(alpha w)),
+//                              and (NORM) the partials of vec_gs_dots(&r', 1, r').  eta not positive: no store.
+//   k_vec_sum_staged           k_vec_dots2's sum of one vector's partials, in its order and to its bits, from LDS.
 // Products and sums are rounded one by one (contraction off): the numpy expressions of the tests to the bit.
 #include <hip/hip_runtime.h>
 
@@ -208,6 +212,106 @@ bool vec_gs_update(double* Y, const double* const* V, int nb, const double* C, i
     k0 += nk;
   } while (k0 < nb);
   if (norm2) hipLaunchKernelGGL(k_vec_dots2, dim3(1), dim3(64), 0, s, work, nwg, 1, norm2);
+  HIPCHK(hipGetLastError());
+  return true;
+}
+
+// The step of the flexible CG: alpha = pi / eta from the two doubles S on the device, x += alpha p, r -= alpha w on the
+// entries a lane of k_vec_update owns.  GO false (eta not positive, or NaN): nothing is stored, and the squares summed are
+// those of r as it is.
+template <bool NORM, bool VEC>
+__device__ __forceinline__ void vec_step_rows(double* X, double* R, const double* __restrict__ P, const double* __restrict__ Wv,
+                                              bool go, double alpha, int64_t lo, int64_t hi, int t, double& a0, double& a1) {
+  for (int64_t e = lo + 2 * t; e < hi; e += 2 * KRY_THREADS) {
+    const bool pair = e + 1 < hi;
+    double r0, r1;
+    kry_load2<VEC>(R, e, pair, r0, r1);
+    if (go) {
+      double x0, x1, p0, p1, w0, w1;
+      kry_load2<VEC>(X, e, pair, x0, x1);
+      kry_load2<VEC>(P, e, pair, p0, p1);
+      kry_load2<VEC>(Wv, e, pair, w0, w1);
+      x0 = __dadd_rn(x0, __dmul_rn(alpha, p0));
+      r0 = __dsub_rn(r0, __dmul_rn(alpha, w0));
+      if (pair) {
+        x1 = __dadd_rn(x1, __dmul_rn(alpha, p1));
+        r1 = __dsub_rn(r1, __dmul_rn(alpha, w1));
+      }
+      if (VEC && pair) {
+        *reinterpret_cast<kry_d2*>(X + e) = kry_d2{x0, x1};
+        *reinterpret_cast<kry_d2*>(R + e) = kry_d2{r0, r1};
+      } else {
+        X[e] = x0;
+        R[e] = r0;
+        if (pair) {
+          X[e + 1] = x1;
+          R[e + 1] = r1;
+        }
+      }
+    }
+    if (NORM) {
+      a0 = __dadd_rn(a0, __dmul_rn(r0, r0));
+      if (pair) a1 = __dadd_rn(a1, __dmul_rn(r1, r1));
+    }
+  }
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(KRY_THREADS) void k_vec_fcg_step(double* X, double* R, const double* __restrict__ P,
+                                                              const double* __restrict__ Wv, const double* __restrict__ S,
+                                                              int n, int rows_per, double* work) {
+  __shared__ double part[KRY_WAVES];
+  const int t = threadIdx.x;
+  const int64_t lo = (int64_t)blockIdx.x * rows_per, hi = min((int64_t)n, lo + rows_per);
+  const double eta = S[0], pi = S[1];
+  const bool go = eta > 0.0;                           // (uniform) false for a NaN too
+  if (!NORM && !go) return;
+  const double alpha = go ? __ddiv_rn(pi, eta) : 0.0;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(P) |
+                         reinterpret_cast<uintptr_t>(Wv);
+  double a0 = 0.0, a1 = 0.0;
+  if ((bits & 15u) == 0) vec_step_rows<NORM, true>(X, R, P, Wv, go, alpha, lo, hi, t, a0, a1);
+  else vec_step_rows<NORM, false>(X, R, P, Wv, go, alpha, lo, hi, t, a0, a1);
+  if (NORM) {
+    const double s = kry_wave_sum(__dadd_rn(a0, a1));
+    if ((t & 63) == 0) part[t >> 6] = s;
+    __syncthreads();
+    if (t == 0) {
+      double r = part[0];
+#pragma unroll
+      for (int v = 1; v < KRY_WAVES; ++v) r = __dadd_rn(r, part[v]);
+      work[blockIdx.x] = r;
+    }
+  }
+}
+
+// The sum k_vec_dots2 makes of the partials of ONE vector -- 0 + work[0] + work[1] + ... in index order, the same bits --
+// with the partials staged in LDS by the whole workgroup first: the one thread that adds them then waits for LDS, not for
+// a global load per term.  nwg <= VEC_DOT_WG.
+__global__ __launch_bounds__(KRY_THREADS) void k_vec_sum_staged(const double* __restrict__ work, int nwg, double* __restrict__ out) {
+  __shared__ double part[VEC_DOT_WG];
+  for (int g = threadIdx.x; g < nwg; g += KRY_THREADS) part[g] = work[g];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+#pragma unroll 16
+    for (int g = 0; g < nwg; ++g) s = __dadd_rn(s, part[g]);
+    out[0] = s;
+  }
+}
+
+bool vec_fcg_step(double* x, double* r, const double* p, const double* w, const double* S, int n, double* norm2, double* work) {
+  if (n < 0 || !x || !r || !p || !w || !S || (norm2 && !work)) throw std::runtime_error("vec_fcg_step: bad argument");
+  if (n == 0 && !norm2) return true;
+  hipStream_t s = (hipStream_t)get_stream();
+  const int nwg = vec_dot_nwg(n), rows_per = vec_dot_rows_per(n);
+  if (nwg > VEC_DOT_WG) throw std::runtime_error("vec_fcg_step: more partial sums than k_vec_sum_staged holds");
+  if (norm2) {
+    hipLaunchKernelGGL((k_vec_fcg_step<true>), dim3(nwg), dim3(KRY_THREADS), 0, s, x, r, p, w, S, n, rows_per, work);
+    hipLaunchKernelGGL(k_vec_sum_staged, dim3(1), dim3(KRY_THREADS), 0, s, work, nwg, norm2);
+  } else {
+    hipLaunchKernelGGL((k_vec_fcg_step<false>), dim3(nwg), dim3(KRY_THREADS), 0, s, x, r, p, w, S, n, rows_per, work);
+  }
   HIPCHK(hipGetLastError());
   return true;
 }

@@ -102,7 +102,8 @@ class GenEOPC:
         out = {}
         for kv in self.lib.PCGenEOGetOptionsString(self.h).decode().split(";"):
             k, _, v = kv.partition("=")
-            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type", "ksp_matsolve_type", "ksp_pc_side"):
+            if k in ("dls1_pc", "els2_pc", "ksp_type", "dls1_ksp_type", "ksp_matsolve_type", "ksp_pc_side",
+                     "ksp_fcg_truncation_type", "ksp_norm_type"):
                 out[k] = v
             elif k == "dls1_cheb_safety":
                 out[k] = tuple(float(t) for t in v.split(","))
@@ -306,6 +307,17 @@ class GenEOPC:
             raise GenEOError("PCGenEOGetKrylovInfo: bad handle")
         return dict(basis_vectors=s.value, basis_bytes=b.value, gs_fused=v[0].value, gs_composed=v[1].value,
                     pc_applies=v[2].value, mat_mults=v[3].value)
+
+    def fcg_info(self):
+        """PCGenEOGetFcgInfo: direction / product pairs and device bytes the flexible CG (-ksp_type fcg) holds now, since the
+        set-up its steps through the fused kernel and through its composed form, and of the last fcg solve the largest
+        window and the downloads the host waited for."""
+        d, b, w = C.c_int(0), C.c_double(0.0), C.c_int(0)
+        v = [C.c_longlong(0) for _ in range(3)]
+        if self.lib.PCGenEOGetFcgInfo(self.h, C.byref(d), C.byref(b), C.byref(v[0]), C.byref(v[1]), C.byref(w), C.byref(v[2])) < 0:
+            raise GenEOError("PCGenEOGetFcgInfo: bad handle")
+        return dict(directions=d.value, bytes=b.value, steps_fused=v[0].value, steps_composed=v[1].value,
+                    max_window=w.value, downloads=v[2].value)
 
     def coarse_block_counters(self):
         """PCGenEOGetCoarseBlockCounters since the set-up: slab applications of E^-1 by the blocked sweeps on the whole block,

@@ -184,7 +184,7 @@ PetscErrorCode PCGenEOSetRHS(GENEO_PC pc, const double* b_dev);
  *      drives PCApply_GenEO instead when PETSc is present) ----------------------------------- */
 PetscErrorCode KSPSolve_GenEO(GENEO_PC pc, const double* b_dev, double* x_dev, int* its, double* rnorm, int* reason);
 int PCGenEOGetResidualHistory(GENEO_PC pc, double* hist, int cap);
-/* -ksp_type cg|gmres|fgmres and -ksp_pc_side left|right (default left) choose the method of KSPSolve_GenEO.  cg and gmres are
+/* -ksp_type cg|gmres|fgmres|fcg (fcg: below) and -ksp_pc_side left|right (default left) choose the method of KSPSolve_GenEO.  cg and gmres are
  * left-preconditioned: their convergence test, rnorm and residual history are those of the preconditioned residual.
  * -ksp_type gmres -ksp_pc_side right is restarted GMRES on A M^-1; -ksp_type fgmres is flexible GMRES, always right, which
  * keeps z_k = M^-1 v_k of every step and so allows a preconditioner that changes between applications (-dls1_ksp_type cg at
@@ -207,6 +207,26 @@ int PCGenEOGetResidualHistory(GENEO_PC pc, double* hist, int cap);
  * Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
 int PCGenEOGetKrylovInfo(GENEO_PC pc, int* basis_vectors, double* basis_bytes, long long* gs_fused, long long* gs_composed,
                          long long* pc_applies, long long* mat_mults);
+/* -ksp_type fcg is the flexible CG of Notay (PETSc KSPFCG): left-preconditioned like cg, with cg's norms and short
+ * recurrences, for the symmetric modes (ASM, SRAS, SORAS and their hybrids) under a preconditioner that changes between
+ * applications.  A new direction is made conjugate to the m_i = min(i, mi) most recent ones, mi = max(1, i mod (mmax + 1))
+ * (-ksp_fcg_truncation_type notay, the default) or mi = mmax (standard), -ksp_fcg_mmax mmax >= 1 (default 30); mmax + 1
+ * directions and their products are held at most, each allocated when a step first needs it, all freed with the set-up.
+ * Per iteration one pass gives the window's dot products and (z, z), one all-reduce and ONE download follow; the step
+ * x += alpha p, r -= alpha A p takes alpha = (r, p) / (A p, p) from the device.  (A p, p) <= 0 leaves x and r untouched
+ * and is reported as KSP_DIVERGED_INDEFINITE_MAT (-8) with the its of that iteration.
+ * -ksp_norm_type preconditioned|unpreconditioned (default preconditioned): unpreconditioned tests, reports and records
+ * |b - A x|, relative to |b| with -ksp_initial_guess_nonzero; it is accepted with fcg only -- KSPSolve_GenEO with any other
+ * -ksp_type, and KSPMatSolve_GenEO, refuse it.  -ksp_pc_side right with fcg is refused when either option is set;
+ * KSPMatSolve_GenEO has no block form of it.
+ * PCGenEOGetFcgInfo: *directions direction / product pairs held now and *bytes the device bytes of everything the method
+ * holds (both 0 before the first fcg solve of a set-up); since the set-up the steps through the fused kernel, *steps_fused,
+ * and through its composed form, *steps_composed (GeneoSetKernelVariant("krylov_fused", 0), or a backend without the
+ * kernel); of the last fcg solve the largest window, *max_window, and the device-to-host copies the host waited for,
+ * *downloads.  PCGenEOGetKrylovInfo's *pc_applies and *mat_mults count an fcg solve too; its other fields do not.
+ * Any pointer may be NULL.  Returns 0, -1 for a bad handle. */
+int PCGenEOGetFcgInfo(GENEO_PC pc, int* directions, double* bytes, long long* steps_fused, long long* steps_composed,
+                      int* max_window, long long* downloads);
 
 /* ---- blocks of right-hand sides (-geneo_block_width 16 | 32; needs -dls1_ksp_type chebyshev) --------------------------
  * The counterparts of pc->ops->matapply, MatMatMult on the MATIS operator and KSPMatSolve.  Blocks are column-major with a

@@ -1,0 +1,72 @@
+"""-m gpu: flexible CG of KSPSolve_GenEO (-ksp_type fcg) on the device, HIP library, no fallback: the checks of
+tests/fcg_util.py that the host twin runs too -- the step kernel of csrc/krylov_dev.hip (fused: numpy's separately rounded
+arithmetic to the bit, norm2 with the bits of vec_gs_dots, nothing written when eta is not positive; composed under
+GeneoSetKernelVariant("krylov_fused", 0): within the derived bounds), the options, the method against the numpy reference,
+the truncation window, fcg against cg, a preconditioner that changes between applications, the counters (one download per
+iterate in the fused form), and cg and gmres before and after."""
+import pytest
+
+import block_rhs_util as U
+import fcg_util as F
+import krylov_right_util as K
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from geneo4petsc_amd import _lib
+    lib = _lib.load()          # raises if the HIP library is missing: no fallback
+    yield lib
+    U.release_pcs(lib)
+
+
+def test_options(lib):
+    F.check_options(lib)
+
+
+@pytest.mark.parametrize("composed", [False, True])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1025, K.BIG])
+def test_vec_fcg_step(lib, n, composed):
+    assert n in K.sizes(lib)
+    F.check_fcg_step(lib, n, composed=composed)
+
+
+@pytest.mark.parametrize("guess,norm", F.CONFIGS)
+@pytest.mark.parametrize("lvl,n", F.CASES)
+def test_against_the_numpy_reference(lib, lvl, n, guess, norm):
+    F.check_case(lib, lvl, n, guess, norm)
+
+
+@pytest.mark.parametrize("mmax,trunc", F.TRUNC)
+def test_truncation(lib, mmax, trunc):
+    F.check_truncation(lib, mmax, trunc)
+
+
+def test_the_window_matters_in_the_reference(lib):
+    F.check_window_matters(lib)
+
+
+@pytest.mark.parametrize("guess", [0, 1])
+@pytest.mark.parametrize("lvl,n", F.EQUALS_CG)
+def test_fcg_equals_cg_on_a_fixed_symmetric_preconditioner(lib, lvl, n, guess):
+    F.check_equals_cg(lib, lvl, n, guess)
+
+
+def test_fcg_against_cg_on_sras_is_reported(lib):
+    """SRAS,1: measured and printed only (the histories of cg and fcg part by 1e-8 to 1e-6 of the first norm there)"""
+    for guess in (0, 1):
+        F.measure_equals_cg(lib, "SRAS,1", 12, guess)
+
+
+@pytest.mark.parametrize("lvl,n", F.NONLINEAR)
+def test_flexible_with_a_changing_preconditioner(lib, lvl, n):
+    F.check_nonlinear(lib, lvl, n)
+
+
+def test_counters(lib):
+    F.check_counters(lib, on_gpu=True)
+
+
+def test_other_methods_are_not_disturbed(lib):
+    F.check_disturbs_nothing(lib, "SRAS,1", 12)
